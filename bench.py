@@ -7,7 +7,9 @@ EOS, so this is the natural, no-work-skipped length).  Inputs are resident in HB
 Utterance batches shard embarrassingly over ranks (no data-path collective); torch.distributed is used only
 for the barrier and the max-over-ranks of the elapsed time.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN for the fields `roofline` and `cpu_baseline`).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps passes and prints the headline; --full adds the
+secondary workloads, the per-kernel rooflines and the CPU baseline (see README/DESIGN for the fields `roofline` and `cpu_baseline`).
+--dump-outputs DIR writes what the last timed pass returned (see dump_outputs).
 """
 import argparse
 import json
@@ -46,11 +48,38 @@ def under_rocprof() -> bool:
     return w.runtime.under_rocprof()
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # per dumped array; with the ids the whole dump stays under 64 MB
+
+
+def dump_outputs(out_dir, hidden, ids):
+    """The last timed pass's results as float32 .npy files: `ids` = greedy token ids [B, max_length] (exact in float32), and
+    `encoder_hidden` = the encoder output [B, S, d] the decoder attended to -- in full while it fits DUMP_BUDGET_BYTES, else a fixed
+    sample of it (flat indices drawn with seed 0, sorted).  Same arguments -> same inputs, so two builds compare file for file."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "ids.npy"), ids.cpu().numpy().astype(np.float32))
+    if hidden is None:
+        return
+    flat = hidden.reshape(-1)
+    n_max = DUMP_BUDGET_BYTES // 4
+    if flat.numel() > n_max:
+        idx = np.sort(np.random.default_rng(0).choice(flat.numel(), n_max, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, "encoder_hidden.npy"), flat.cpu().numpy())
+    else:
+        np.save(os.path.join(out_dir, "encoder_hidden.npy"), hidden.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed passes")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true", help="also run the secondary measurements (32-token transcripts, batch 16, the "
+                    "variable-length workload, several workers per GPU, fp16 engines, per-kernel rooflines, CPU baseline); the --no-* "
+                    "options below select among them.  Without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed pass returned as DIR/<name>.npy (float32)")
     ap.add_argument("--model", default="whisper-medium.en")
     ap.add_argument("--batch", type=int, default=8, help="utterances per GPU")
     ap.add_argument("--max-length", type=int, default=448)
@@ -74,6 +103,10 @@ def main():
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal only: map every rank onto the visible GPUs round-robin")
     ap.add_argument("--all-legs", action="store_true", help="with --gpus N > 1: also run the secondary legs (default there: the timed headline leg only)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_varlen = args.no_batch16 = args.no_fp16_decoder = args.no_two_workers = args.no_roofline = args.no_cpu_baseline = True
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and not args.all_legs:
         # A multi-GPU run measures the scaling of the HEADLINE: the secondary legs (variable-length workload, batch 16, fp16 engines, up to
         # 4 worker threads per rank, per-kernel rooflines, CPU baseline) only lengthen an 8-GPU lease for numbers that are read at N = 1.
@@ -129,7 +162,7 @@ def main():
 
     def one_pass(force_eos_step=None):
         hidden = enc(mel)
-        return dec.generate(hidden, force_eos_step=force_eos_step)
+        return hidden, dec.generate(hidden, force_eos_step=force_eos_step)
 
     def barrier():
         torch.cuda.synchronize()
@@ -141,37 +174,42 @@ def main():
         barrier()
         t = time.perf_counter()
         for _ in range(n):
-            ids = one_pass(**kw)
+            hidden, ids = one_pass(**kw)   # the decoder holds `hidden` until the next pass anyway: keeping it costs no memory
         torch.cuda.synchronize()
         el = time.perf_counter() - t
         el = w.sharding.max_over_ranks(el, dist)
         barrier()
-        return el, ids
+        return el, hidden, ids
 
     if args.workers > 1:   # opt-in: the K timed steps handed to N workers (each step is still one pass over one batch of B utterances)
         head_pipe = w.WhisperPipeline(enc_blob, dec_blob, cfg, workers=args.workers)
         head_pipe.transcribe([mel] * max(args.warmup, args.workers))
         barrier()
         t = time.perf_counter()
-        ids = head_pipe.transcribe([mel] * args.steps)[-1]
+        hidden, ids = None, head_pipe.transcribe([mel] * args.steps)[-1]   # the pipeline returns ids only
         torch.cuda.synchronize()
         elapsed = w.sharding.max_over_ranks(time.perf_counter() - t, dist)
         barrier()
         del head_pipe
     else:
         for _ in range(args.warmup):
-            ids = one_pass()
-        elapsed, ids = timed(args.steps)
+            one_pass()
+        elapsed, hidden, ids = timed(args.steps)
     assert ids.shape == (B, args.max_length), ids.shape
     audio_s = 30.0 * B * world * args.steps
     value = audio_s / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hidden, ids)
+    del hidden
 
     # secondary figure: LibriSpeech-like transcript length (EOS forced at decoder step 32)
-    one_pass(force_eos_step=32)
-    n32_passes = max(1, min(args.steps, 5))
-    el32, ids32 = timed(n32_passes, force_eos_step=32)
-    value_n32 = 30.0 * B * world * n32_passes / el32
+    value_n32 = None
+    if args.full:
+        one_pass(force_eos_step=32)
+        n32_passes = max(1, min(args.steps, 5))
+        el32 = timed(n32_passes, force_eos_step=32)[0]
+        value_n32 = 30.0 * B * world * n32_passes / el32
 
     # secondary figure: 16 utterances per GPU in one engine batch (the decode step is launch-latency bound at B = 8, so
     # throughput still grows with the batch; BASELINE config 4 uses B = 16)
@@ -360,7 +398,7 @@ def main():
                                     "as accurate as the fp32 MFMA instruction (tests/test_gpu_kernels.py::test_gemm_x3_is_an_fp32_gemm)"
                                     if enc.session._lib.wt_engine_gemm_mode(enc.session.handle) == 1 else "native MFMA of the engine's precision"),
                    "batch_per_gpu": B, "workers_per_gpu": args.workers, "decode_steps": args.max_length - 1, "sharding": f"utterance-parallel x{world}, no collective",
-                   "value_n32_decode_steps": round(value_n32, 2),
+                   "value_n32_decode_steps": round(value_n32, 2) if value_n32 else None,
                    "value_batch16_per_gpu": round(value_b16, 2) if value_b16 else None,
                    "value_varlen": varlen["length_sorted"]["value"] if varlen else None,
                    "value_varlen_continuous": varlen["dataset_order_continuous"]["value"] if varlen else None,

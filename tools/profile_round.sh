@@ -15,13 +15,13 @@ step() { echo "[profile_round] $*"; }
 if [ "$PHASE" = all ] || [ "$PHASE" = bench ]; then
 # ---- plain bench lines (no profiler): headline config, then BASELINE configs 2, 3, 4
 step "bench medium.en B=8 (headline)"
-timeout -k 10 400 python3 $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || exit 1
 step "bench config 4 (medium.en fp16 encoder + fp32 decoder, B=16)"
-timeout -k 10 400 python3 $R/bench.py --encoder-precision float16 --batch 16 --no-batch16 --no-cpu-baseline > $O/${TAG}_cfg4_bench.json 2> $O/${TAG}_cfg4_bench.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full --encoder-precision float16 --batch 16 --no-batch16 --no-cpu-baseline > $O/${TAG}_cfg4_bench.json 2> $O/${TAG}_cfg4_bench.err || exit 1
 step "bench config 3 (small.en B=8)"
-timeout -k 10 300 python3 $R/bench.py --model whisper-small.en --no-batch16 --no-cpu-baseline > $O/${TAG}_cfg3_bench.json 2> $O/${TAG}_cfg3_bench.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --model whisper-small.en --no-batch16 --no-cpu-baseline > $O/${TAG}_cfg3_bench.json 2> $O/${TAG}_cfg3_bench.err || exit 1
 step "bench config 2 (tiny.en B=1)"
-timeout -k 10 300 python3 $R/bench.py --model whisper-tiny.en --batch 1 --no-batch16 --no-cpu-baseline > $O/${TAG}_cfg2_bench.json 2> $O/${TAG}_cfg2_bench.err || exit 1
+timeout -k 10 300 python3 $R/bench.py --full --model whisper-tiny.en --batch 1 --no-batch16 --no-cpu-baseline > $O/${TAG}_cfg2_bench.json 2> $O/${TAG}_cfg2_bench.err || exit 1
 
 fi
 # ---- kernel traces (rocprofv3 --kernel-trace --stats), summaries by tools/prof_summary.py
@@ -30,7 +30,7 @@ trace() {  # name, bench args...
     export WT_SAVE_MAPS=$O/${TAG}_${name}_proc_maps.txt   # load addresses of every module of the profiled process: any crash trace of this run stays symbolisable
     step "kernel trace $name"
     rm -rf $O/${TAG}_trace_$name
-    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace_$name -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-batch16 --no-varlen --no-fp16-decoder "$@" > $O/${TAG}_${name}_bench_under_rocprof.json 2> $O/${TAG}_trace_$name.err || return 1
+    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace_$name -- python3 $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-batch16 --no-varlen --no-fp16-decoder "$@" > $O/${TAG}_${name}_bench_under_rocprof.json 2> $O/${TAG}_trace_$name.err || return 1
     local kt=$(find $O/${TAG}_trace_$name -name "*kernel_trace.csv" | head -1)
     local ks=$(find $O/${TAG}_trace_$name -name "*kernel_stats.csv" | head -1)
     python3 $R/tools/prof_summary.py $kt > $O/${TAG}_${name}_kernel_trace_summary.txt
@@ -52,7 +52,7 @@ pmc() {  # name, counters..., --, bench args
     shift
     step "pmc $name: ${ctr[*]}"
     rm -rf $O/${TAG}_pmc_$name
-    timeout -k 10 600 rocprofv3 --kernel-trace --pmc "${ctr[@]}" --output-format csv -d $O/${TAG}_pmc_$name -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-batch16 --no-roofline --no-varlen --no-fp16-decoder "$@" > /dev/null 2> $O/${TAG}_pmc_$name.err || return 1
+    timeout -k 10 600 rocprofv3 --kernel-trace --pmc "${ctr[@]}" --output-format csv -d $O/${TAG}_pmc_$name -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-batch16 --no-roofline --no-varlen --no-fp16-decoder "$@" > /dev/null 2> $O/${TAG}_pmc_$name.err || return 1
 }
 if [ "$PHASE" = all ] || [ "$PHASE" = pmc ]; then
 pmc fetch FETCH_SIZE -- --max-length 12 || exit 1
