@@ -8,6 +8,7 @@
  */
 #ifndef WHISPER_TRTLLM_AMD_DEBUG_H
 #define WHISPER_TRTLLM_AMD_DEBUG_H
+#include <stddef.h>
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -83,6 +84,31 @@ int wt_dbg_skinny_pair_f16(const float* Xa, const void* Wa, const float* bias_a,
  * K / V caches [B][H][kv_cap][64], rows [seq_off, seq_off + rows), stored as half (out_half) or f32 */
 int wt_dbg_gemm_f16_kv(const void* A, int rows_total, const void* W, const float* bias, void* kcache, void* vcache, int B, int rows, int H,
                        int kv_cap, int seq_off, int out_half, void* stream);
+
+/* launch_gemm_x3 with its tile instantiation forced: tile 128 (128x128), 192 (192x256), 256 (256x256), 0 = by shape (as wt_dbg_gemm_x3) */
+int wt_dbg_gemm_x3_tile(const float* A, const float* W, const float* bias, const float* resid, void* C, int M, int N, int K, int act,
+                        void* a_planes, void* w_planes, int flags, int tile, void* stream);
+/* LayerNorm (eps 1e-5) of x [rows][d] written as three bf16 planes [3][rows][d] (b1 = rn(y), b2 = rn(y - b1), b3 = rn(y - b1 - b2)) */
+int wt_dbg_layernorm_split(const float* x, const float* w, const float* b, void* planes, int rows, int d, void* stream);
+
+/* The encoder's two convolutions exactly as an fp32 / fp16 engine launches them (the same GemmParams helpers, wt_common.h), mel
+ * [B][C][2S] -> out [B][S][d] float: conv1 (k 3, pad 1) + GELU, conv2 (k 3, stride 2, pad 1) + GELU + pos [S][d].
+ * mode 0: fp32 MFMA (float weights [d][3C] / [d][3d] in the converter's layout), 1: x3 (the weights given as three bf16 planes each,
+ * plane p at + p * d * 3C / d * 3d elements), 2: fp16 (half weights).  tile: x3 only, as wt_dbg_gemm_x3_tile.
+ * scratch (wt_dbg_encoder_convs_scratch_bytes): melT at offset 0, c1 at offset c1_off = align_up(n_melT * esz, 256), with
+ *   n_melT = B (2S + 2) C + 4 C and n_c1 = B (2S + 2) d + 4 d elements, esz = 6 in mode 1 (three bf16 planes of n elements each,
+ *   plane p at + 2 p n bytes), else 4 (mode 0: float; mode 2: half data at the start of the region).  Utterance b's rows sit at
+ *   b (2S + 2) + r: row t + 1 holds frame t (melT) / conv1's output at frame t (c1), rows 0 and 2S + 1 are the zero padding.
+ * Every call first clears both regions (what the engine does when its workspace grows), then runs the three launches. */
+size_t wt_dbg_encoder_convs_scratch_bytes(int B, int C, int S, int d, int mode);
+int wt_dbg_encoder_convs(const float* mel, const void* conv1_w, const float* conv1_b, const void* conv2_w, const float* conv2_b, const float* pos,
+                         float* out, void* scratch, int B, int C, int S, int d, int mode, int tile, void* stream);
+/* One decoder layer's cross-K/V projection as the engine launches it: A f32 [B][rows_total][H*64] (the first `rows` rows of every
+ * utterance), W f32 [2*H*64][H*64], bias [2*H*64] -> f32 caches [layer_rows][H][cap][64], utterance b at cache row row0 + b, sequence rows
+ * [seq_off, seq_off + rows); nothing else is written.  mode 0: fp32 MFMA, 1: x3 (scratch: A's planes at 0, 6 B rows_total H*64 bytes,
+ * then W's planes at the next multiple of 256 bytes, 12 (H*64)^2 bytes); tile as wt_dbg_gemm_x3_tile. */
+int wt_dbg_cross_kv(const float* A, int rows_total, const float* W, const float* bias, float* kcache, float* vcache, void* scratch, int B, int rows,
+                    int H, int cap, int seq_off, int layer_rows, int row0, int mode, int tile, void* stream);
 
 #ifdef __cplusplus
 }

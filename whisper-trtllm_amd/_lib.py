@@ -23,7 +23,8 @@ EXPORTS = [
 ]
 DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_gemm_f16", "wt_dbg_gemm_f16_variant", "wt_dbg_layernorm", "wt_dbg_encoder_attention", "wt_dbg_encoder_attention_split", "wt_dbg_encoder_attention_x3", "wt_dbg_encoder_attention_f16", "wt_dbg_skinny", "wt_dbg_skinny_gelu_in", "wt_dbg_encoder_attention_occupancy", "wt_dbg_decode_attention",
                  "wt_dbg_decode_attention_folded", "wt_dbg_skinny_pair", "wt_dbg_attention_then_projection", "wt_dbg_self_attention_then_pair",
-                 "wt_dbg_skinny_f16", "wt_dbg_decode_attention_f16", "wt_dbg_attention_then_projection_f16", "wt_dbg_skinny_pair_f16", "wt_dbg_gemm_f16_kv"]
+                 "wt_dbg_skinny_f16", "wt_dbg_decode_attention_f16", "wt_dbg_attention_then_projection_f16", "wt_dbg_skinny_pair_f16", "wt_dbg_gemm_f16_kv",
+                 "wt_dbg_gemm_x3_tile", "wt_dbg_layernorm_split", "wt_dbg_encoder_convs_scratch_bytes", "wt_dbg_encoder_convs", "wt_dbg_cross_kv"]
 
 
 class TensorDesc(Structure):
@@ -128,6 +129,12 @@ def load():
     lib.wt_dbg_attention_then_projection_f16.argtypes = [P, P, P, P, P, P, P, P, I, I, I, I, P]
     lib.wt_dbg_skinny_pair_f16.argtypes = lib.wt_dbg_skinny_pair.argtypes
     lib.wt_dbg_gemm_f16_kv.argtypes = [P, I, P, P, P, P, I, I, I, I, I, I, P]
+    lib.wt_dbg_gemm_x3_tile.argtypes = [P, P, P, P, P, I, I, I, I, P, P, I, I, P]
+    lib.wt_dbg_layernorm_split.argtypes = [P, P, P, P, I, I, P]
+    lib.wt_dbg_encoder_convs_scratch_bytes.argtypes = [I, I, I, I, I]
+    lib.wt_dbg_encoder_convs_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_encoder_convs.argtypes = [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]
+    lib.wt_dbg_cross_kv.argtypes = [P, I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

@@ -26,8 +26,8 @@ extern "C" int wt_dbg_gemm_stamps(const float* A, int lda, const float* W, const
 }
 // fp32 GEMM on the bf16 matrix cores (launch_gemm_x3): the hook splits A and W into the caller's scratch planes (3 * M * K and 3 * N * K
 // bf16) and multiplies; flags bit 0: C receives three bf16 planes of [M][N] instead of fp32; bit 1: skip the splitting (planes in place)
-extern "C" int wt_dbg_gemm_x3(const float* A, const float* W, const float* bias, const float* resid, void* C, int M, int N, int K, int act,
-                              void* a_planes, void* w_planes, int flags, void* stream) {
+extern "C" int wt_dbg_gemm_x3_tile(const float* A, const float* W, const float* bias, const float* resid, void* C, int M, int N, int K, int act,
+                                   void* a_planes, void* w_planes, int flags, int tile, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     const int out_split = flags & 1;
     int rc = 0;
@@ -40,11 +40,76 @@ extern "C" int wt_dbg_gemm_x3(const float* A, const float* W, const float* bias,
     g.A = (const float*)a_planes; g.lda = K; g.a_rows_per_batch = M; g.a_plane = (long long)M * K; g.W = (const float*)w_planes; g.w_plane = (long long)N * K;
     g.bias = bias; g.resid = resid; g.C = (float*)C; g.ldc = N; g.c_rows_per_batch = M; g.M = M; g.N = N; g.K = K; g.act = act;
     g.out_split = out_split; g.c_plane = (long long)M * N;
-    return rc_of(launch_gemm_x3(g, s));
+    return rc_of(launch_gemm_x3(g, s, tile));
+}
+extern "C" int wt_dbg_gemm_x3(const float* A, const float* W, const float* bias, const float* resid, void* C, int M, int N, int K, int act,
+                              void* a_planes, void* w_planes, int flags, void* stream) {
+    return wt_dbg_gemm_x3_tile(A, W, bias, resid, C, M, N, K, act, a_planes, w_planes, flags, 0, stream);
 }
 extern "C" int wt_dbg_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int d, void* stream) {
     return rc_of(launch_layernorm(x, w, b, y, rows, d, (hipStream_t)stream));
 }
+extern "C" int wt_dbg_layernorm_split(const float* x, const float* w, const float* b, void* planes, int rows, int d, void* stream) {
+    return rc_of(launch_layernorm_split(x, w, b, planes, (size_t)rows * d, rows, d, (hipStream_t)stream));
+}
+
+// ---- the encoder's two convolutions and the cross-K/V projection, parameterised by the engine's own helpers (wt_common.h) ----
+static size_t conv_scratch_layout(int B, int S, int C, int d, int mode, size_t& n_melT, size_t& n_c1, size_t& c1_off) {
+    conv_ws_elems(B, S, C, d, n_melT, n_c1);
+    const size_t esz = mode == CONV_X3 ? 6 : 4;
+    c1_off = (n_melT * esz + 255) & ~(size_t)255;
+    return c1_off + n_c1 * esz;
+}
+extern "C" size_t wt_dbg_encoder_convs_scratch_bytes(int B, int C, int S, int d, int mode) {
+    size_t n_melT, n_c1, c1_off;
+    return conv_scratch_layout(B, S, C, d, mode, n_melT, n_c1, c1_off);
+}
+extern "C" int wt_dbg_encoder_convs(const float* mel, const void* conv1_w, const float* conv1_b, const void* conv2_w, const float* conv2_b,
+                                    const float* pos, float* out, void* scratch, int B, int C, int S, int d, int mode, int tile, void* stream) {
+    if (B < 1 || S < 1 || C < 1 || C > 128 || d < 1 || mode < CONV_F32 || mode > CONV_F16 || (tile && mode != CONV_X3)) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    size_t n_melT, n_c1, c1_off;
+    conv_scratch_layout(B, S, C, d, mode, n_melT, n_c1, c1_off);
+    char* melT = (char*)scratch;
+    char* c1 = melT + c1_off;
+    GemmParams c1g, c2g;
+    conv_gemm_params(mode, melT, n_melT, c1, n_c1, conv1_w, conv1_b, conv2_w, conv2_b, pos, out, B, S, C, d, c1g, c2g);
+    if (mode == CONV_X3 && !(gemm_x3_usable(c1g) && gemm_x3_usable(c2g))) return -22;
+    int rc = rc_of(conv_ws_clear(melT, n_melT, c1, n_c1, mode == CONV_X3 ? 6 : 4, s));
+    if (rc) return rc;
+    const int Fr = 2 * S;
+    if (mode == CONV_X3) {
+        if ((rc = rc_of(launch_mel_transpose_split(mel, melT, n_melT, B, C, Fr, s)))) return rc;
+        if ((rc = rc_of(launch_gemm_x3(c1g, s, tile)))) return rc;
+        return rc_of(launch_gemm_x3(c2g, s, tile));
+    }
+    if (mode == CONV_F16) {
+        if ((rc = rc_of(launch_mel_transpose_h(mel, melT, B, C, Fr, s)))) return rc;
+        if ((rc = rc_of(launch_gemm_f16(c1g, true, s)))) return rc;
+        return rc_of(launch_gemm_f16(c2g, false, s));
+    }
+    if ((rc = rc_of(launch_mel_transpose(mel, (float*)melT, B, C, Fr, s)))) return rc;
+    if ((rc = rc_of(launch_gemm_f32(c1g, s)))) return rc;
+    return rc_of(launch_gemm_f32(c2g, s));
+}
+extern "C" int wt_dbg_cross_kv(const float* A, int rows_total, const float* W, const float* bias, float* kcache, float* vcache, void* scratch,
+                               int B, int rows, int H, int cap, int seq_off, int layer_rows, int row0, int mode, int tile, void* stream) {
+    if (B < 1 || rows < 1 || rows > rows_total || seq_off < 0 || seq_off + rows > cap || row0 < 0 || row0 + B > layer_rows || mode < 0 || mode > 1 ||
+        (tile && mode != 1))
+        return -22;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = H * HEAD_DIM;
+    GemmParams g = cross_kv_gemm_params(A, rows_total, W, bias, kcache, vcache, 4, B, rows, H, cap, seq_off, row0);
+    if (mode == 0) return rc_of(launch_gemm_f32(g, s));
+    const size_t a_plane = (size_t)B * rows_total * d;
+    char* w3 = (char*)scratch + ((a_plane * 6 + 255) & ~(size_t)255);
+    int rc = rc_of(launch_split3(A, scratch, a_plane, a_plane, s));
+    if (rc || (rc = rc_of(launch_split3(W, w3, 2 * (size_t)d * d, 2 * (size_t)d * d, s)))) return rc;
+    cross_kv_x3(g, scratch, a_plane, w3);
+    if (!gemm_x3_usable(g)) return -22;
+    return rc_of(launch_gemm_x3(g, s, tile));
+}
+
 extern "C" int wt_dbg_encoder_attention(const float* qkv, float* ctx, int B, int S, int H, void* stream) {
     return rc_of(launch_encoder_attention(qkv, ctx, B, S, H, (hipStream_t)stream));
 }

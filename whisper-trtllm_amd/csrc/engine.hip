@@ -436,16 +436,17 @@ extern "C" int wt_engine_gemm_mode(const wt_engine* e) { return e && e->use_x3 ?
 static int enc_reserve(wt_engine* e, int B, hipStream_t s) {
     if (B <= e->enc_cap) return WT_OK;
     if (e->enc_ws) { hipFree(e->enc_ws); e->enc_ws = nullptr; e->enc_cap = 0; }
-    const size_t Fr = 2 * (size_t)e->S, M = (size_t)B * e->S, d = e->d;
+    const size_t M = (size_t)B * e->S, d = e->d;
     size_t off = 0;
     auto take = [&](size_t floats) { size_t o = off; off = align_up(off + floats * 4, 256); return o; };
-    const size_t o_melT = take((size_t)B * (Fr + 2) * e->C + 4 * e->C);
-    const size_t o_c1 = take((size_t)B * (Fr + 2) * d + 4 * d);
+    size_t n_melT, n_c1;   // elements (per plane)
+    conv_ws_elems(B, e->S, e->C, e->d, n_melT, n_c1);
+    const size_t o_melT = take(n_melT);
+    const size_t o_c1 = take(n_c1);
     const size_t o_h = take(M * d), o_x = take(M * d), o_qkv = take(M * 3 * d), o_ctx = take(M * d), o_ffn = take(M * e->F);
     // x3 GEMMs: their A operands as three bf16 planes (6 bytes per element = 1.5 floats)
     const size_t o_xs3 = take(e->use_x3 ? (M * d * 3 + 1) / 2 : 0), o_ctx3 = take(e->use_x3 ? (M * d * 3 + 1) / 2 : 0), o_ffn3 = take(e->use_x3 ? (M * e->F * 3 + 1) / 2 : 0);
     const size_t o_qkv3 = take(e->use_x3 ? (M * 3 * d * 3 + 1) / 2 : 0);
-    const size_t n_melT = (size_t)B * (Fr + 2) * e->C + 4 * e->C, n_c1 = (size_t)B * (Fr + 2) * d + 4 * d;   // elements per plane
     const size_t o_melT3 = take(e->conv1_w3 ? (n_melT * 3 + 1) / 2 : 0), o_c1_3 = take(e->conv1_w3 ? (n_c1 * 3 + 1) / 2 : 0);
     // fp16 engines reuse the fp32-sized regions for their half-precision activations (half the bytes)
     hipError_t he = hipMalloc((void**)&e->enc_ws, off);
@@ -456,15 +457,11 @@ static int enc_reserve(wt_engine* e, int B, hipStream_t s) {
     e->xs3 = e->enc_ws + o_xs3; e->ctx3 = e->enc_ws + o_ctx3; e->ffn3 = e->enc_ws + o_ffn3; e->qkv3 = e->enc_ws + o_qkv3;
     e->melT3 = e->enc_ws + o_melT3; e->c1_3 = e->enc_ws + o_c1_3;
     e->melT3_plane = n_melT; e->c1_3_plane = n_c1;
-    if (e->conv1_w3) {   // zero padding rows of the plane forms (a bf16 zero is all-zero bits)
-        HIPCHK(hipMemsetAsync(e->melT3, 0, n_melT * 6, s));
-        HIPCHK(hipMemsetAsync(e->c1_3, 0, n_c1 * 6, s));
-    }
+    if (e->conv1_w3) HIPCHK(conv_ws_clear(e->melT3, n_melT, e->c1_3, n_c1, 6, s));   // zero padding rows of the plane forms (a bf16 zero is all-zero bits)
     e->melT_h = e->melT; e->c1_h = e->c1; e->x_h = e->xbuf; e->ffn_h = e->ffn;
     e->ctx_h = (char*)e->ffn + M * e->F * 2;  // second half of the ffn region (M*F*2 bytes >= M*d*2)
     // conv zero-padding rows (row 0 / row F+1 of every utterance) are never written by the kernels below
-    HIPCHK(hipMemsetAsync(e->melT, 0, ((size_t)B * (Fr + 2) * e->C + 4 * e->C) * 4, s));
-    HIPCHK(hipMemsetAsync(e->c1, 0, ((size_t)B * (Fr + 2) * d + 4 * d) * 4, s));
+    HIPCHK(conv_ws_clear(e->melT, n_melT, e->c1, n_c1, 4, s));
     // Growth is rare.  The ABI takes a stream per call: finish the clears before returning, so that a following call on this handle
     // from a DIFFERENT stream cannot overtake them (allowed while other threads capture: thread-local capture mode)
     HIPCHK(hipStreamSynchronize(s));
@@ -498,17 +495,15 @@ static int encoder_forward_f16(wt_engine* e, const float* mel, int B, float* out
         return le == hipSuccess ? WT_OK : fail(WT_E_HIP, "fp16 GEMM launch failed: %s", hipGetErrorString(le));
     };
     LAUNCH(launch_mel_transpose_h(mel, e->melT_h, B, C, Fr, s));
-    GemmParams g;
-    memset(&g, 0, sizeof g);
-    g.A = (const float*)e->melT_h; g.lda = C; g.a_rows_per_batch = Fr; g.a_batch_stride = (long long)(Fr + 2) * C;
-    g.W = e->conv1_w; g.bias = e->conv1_b; g.M = B * Fr; g.N = d; g.K = 3 * C; g.act = 1;
-    g.C = (float*)((char*)e->c1_h + (size_t)d * 2); g.ldc = d; g.c_rows_per_batch = Fr; g.c_batch_stride = (long long)(Fr + 2) * d;
-    if ((rc = hgemm(g, true))) return rc;
-    memset(&g, 0, sizeof g);
-    g.A = (const float*)e->c1_h; g.lda = 2 * d; g.a_rows_per_batch = S; g.a_batch_stride = (long long)(Fr + 2) * d;
-    g.W = e->conv2_w; g.bias = e->conv2_b; g.M = M; g.N = d; g.K = 3 * d; g.act = 1; g.pos = e->enc_pos;
-    g.C = e->hbuf; g.ldc = d; g.c_rows_per_batch = S; g.c_batch_stride = (long long)S * d;
-    if ((rc = hgemm(g, false))) return rc;
+    {
+        size_t n_melT, n_c1;
+        conv_ws_elems(B, S, C, d, n_melT, n_c1);
+        GemmParams c1g, c2g;
+        conv_gemm_params(CONV_F16, e->melT_h, n_melT, e->c1_h, n_c1, e->conv1_w, e->conv1_b, e->conv2_w, e->conv2_b, e->enc_pos, e->hbuf, B, S, C, d,
+                         c1g, c2g);
+        if ((rc = hgemm(c1g, true))) return rc;
+        if ((rc = hgemm(c2g, false))) return rc;
+    }
     auto dense = [&](const void* A, int K, const float* Wt, const float* bias, int N, void* Cout, int act, const float* resid,
                      bool out_half) {
         GemmParams q;
@@ -546,23 +541,16 @@ extern "C" int wt_encoder_forward(wt_engine* e, const float* mel, int B, float* 
     if (rc) return rc;
     const int S = e->S, Fr = 2 * S, d = e->d, C = e->C, M = B * S;
     if (e->precision == WT_F16) return encoder_forward_f16(e, mel, B, out, s);
-    GemmParams g;
     bool convs_x3 = false;
+    size_t n_melT, n_c1;
+    conv_ws_elems(B, S, C, d, n_melT, n_c1);
     if (e->use_x3 && e->conv1_w3) {   // both convolutions as launch_gemm_x3 (operand planes; conv1's GELU output goes out as planes for conv2)
-        const size_t n_melT = e->melT3_plane, n_c1 = e->c1_3_plane;
         GemmParams c1g, c2g;
-        memset(&c1g, 0, sizeof c1g);
-        c1g.A = (const float*)e->melT3; c1g.lda = C; c1g.a_rows_per_batch = Fr; c1g.a_batch_stride = (long long)(Fr + 2) * C; c1g.a_plane = (long long)n_melT;
-        c1g.W = (const float*)e->conv1_w3; c1g.w_plane = (long long)d * 3 * C; c1g.bias = e->conv1_b; c1g.M = B * Fr; c1g.N = d; c1g.K = 3 * C; c1g.act = 1;
-        c1g.C = (float*)((char*)e->c1_3 + (size_t)d * 2); c1g.ldc = d; c1g.c_rows_per_batch = Fr; c1g.c_batch_stride = (long long)(Fr + 2) * d;
-        c1g.out_split = 1; c1g.c_plane = (long long)n_c1;
-        memset(&c2g, 0, sizeof c2g);
-        c2g.A = (const float*)e->c1_3; c2g.lda = 2 * d; c2g.a_rows_per_batch = S; c2g.a_batch_stride = (long long)(Fr + 2) * d; c2g.a_plane = (long long)n_c1;
-        c2g.W = (const float*)e->conv2_w3; c2g.w_plane = (long long)d * 3 * d; c2g.bias = e->conv2_b; c2g.M = M; c2g.N = d; c2g.K = 3 * d; c2g.act = 1; c2g.pos = e->enc_pos;
-        c2g.C = e->hbuf; c2g.ldc = d; c2g.c_rows_per_batch = S; c2g.c_batch_stride = (long long)S * d;
+        conv_gemm_params(CONV_X3, e->melT3, e->melT3_plane, e->c1_3, e->c1_3_plane, e->conv1_w3, e->conv1_b, e->conv2_w3, e->conv2_b, e->enc_pos,
+                         e->hbuf, B, S, C, d, c1g, c2g);
         if (gemm_x3_usable(c1g) && gemm_x3_usable(c2g)) {
             convs_x3 = true;
-            LAUNCH(launch_mel_transpose_split(mel, e->melT3, n_melT, B, C, Fr, s));
+            LAUNCH(launch_mel_transpose_split(mel, e->melT3, e->melT3_plane, B, C, Fr, s));
             for (const GemmParams* q : {&c1g, &c2g}) {
                 hipEvent_t a, b;
                 timer_begin(e, e->t_gemm, s, &a, &b);
@@ -572,19 +560,14 @@ extern "C" int wt_encoder_forward(wt_engine* e, const float* mel, int B, float* 
         }
     }
     if (!convs_x3) {
-    LAUNCH(launch_mel_transpose(mel, e->melT, B, C, Fr, s));
-    memset(&g, 0, sizeof g);
-    // conv1 (k=3, pad 1) + GELU as an implicit GEMM over the time-major padded mel (model.py:78,97)
-    g.A = e->melT; g.lda = C; g.a_rows_per_batch = Fr; g.a_batch_stride = (long long)(Fr + 2) * C;
-    g.W = e->conv1_w; g.bias = e->conv1_b; g.M = B * Fr; g.N = d; g.K = 3 * C; g.act = 1;
-    g.C = e->c1 + d; g.ldc = d; g.c_rows_per_batch = Fr; g.c_batch_stride = (long long)(Fr + 2) * d;
-    if ((rc = timed_gemm(e, g, s))) return rc;
-    // conv2 (k=3, stride 2, pad 1) + GELU + embed_positions, written as [B*S, d] (model.py:79,98-102)
-    memset(&g, 0, sizeof g);
-    g.A = e->c1; g.lda = 2 * d; g.a_rows_per_batch = S; g.a_batch_stride = (long long)(Fr + 2) * d;
-    g.W = e->conv2_w; g.bias = e->conv2_b; g.M = M; g.N = d; g.K = 3 * d; g.act = 1; g.pos = e->enc_pos;
-    g.C = e->hbuf; g.ldc = d; g.c_rows_per_batch = S; g.c_batch_stride = (long long)S * d;
-    if ((rc = timed_gemm(e, g, s))) return rc;
+        LAUNCH(launch_mel_transpose(mel, e->melT, B, C, Fr, s));
+        // conv1 (k=3, pad 1) + GELU as an implicit GEMM over the time-major padded mel (model.py:78,97), then
+        // conv2 (k=3, stride 2, pad 1) + GELU + embed_positions, written as [B*S, d] (model.py:79,98-102)
+        GemmParams c1g, c2g;
+        conv_gemm_params(CONV_F32, e->melT, n_melT, e->c1, n_c1, e->conv1_w, e->conv1_b, e->conv2_w, e->conv2_b, e->enc_pos, e->hbuf, B, S, C, d,
+                         c1g, c2g);
+        if ((rc = timed_gemm(e, c1g, s))) return rc;
+        if ((rc = timed_gemm(e, c2g, s))) return rc;
     }
 
     auto dense = [&](const float* A, int K, const float* Wt, const float* bias, int N, float* Cout, int act,
@@ -856,31 +839,25 @@ static int cross_kv_project(wt_engine* e, const float* enc_hidden, int B, int ro
     const size_t row_bytes = (size_t)e->H * e->S * HEAD_DIM * kv_esz;
     if (e->w_half) LAUNCH(launch_cast_h(enc_hidden, e->enc_h, (size_t)B * e->S * d, s));
     const size_t enc_plane = (size_t)B * e->S * d;
+    const void* A = e->w_half ? (const void*)e->enc_h : (const void*)enc_hidden;
     bool x3 = e->use_x3 && !e->w_half && B <= (e->dec_cap > MAX_ROWS ? e->dec_cap : MAX_ROWS);
     if (x3) {   // the encoder memory as three bf16 planes (the x3 GEMM's A operand)
-        GemmParams t;
-        memset(&t, 0, sizeof t);
-        t.A = (const float*)e->enc3; t.lda = d; t.a_rows_per_batch = rows; t.a_batch_stride = (long long)e->S * d; t.a_plane = (long long)enc_plane;
-        t.W = (const float*)e->dec_layers[0].ckv_w3; t.w_plane = 2ll * d * d; t.M = B * rows; t.N = 2 * d; t.K = d; t.c_rows_per_batch = rows;
+        GemmParams t = cross_kv_gemm_params(A, e->S, e->dec_layers[0].ckv_w, e->dec_layers[0].ckv_b, ck, cv, kv_esz, B, rows, e->H, e->S, seq_off, row0);
+        cross_kv_x3(t, e->enc3, enc_plane, e->dec_layers[0].ckv_w3);
         x3 = gemm_x3_usable(t);
         if (x3) LAUNCH(launch_split3(enc_hidden, e->enc3, enc_plane, enc_plane, s));
     }
     for (int i = 0; i < e->L; ++i) {
         const DecLayerW& l = e->dec_layers[i];
-        const size_t layer = ((size_t)i * layer_rows + row0) * row_bytes;
-        GemmParams g;
-        memset(&g, 0, sizeof g);
-        g.A = e->w_half ? (const float*)e->enc_h : enc_hidden; g.lda = d; g.a_rows_per_batch = rows; g.a_batch_stride = (long long)e->S * d;
-        g.W = l.ckv_w; g.bias = l.ckv_b; g.M = B * rows; g.N = 2 * d; g.K = d;
-        g.epi = EPI_KV_HEADS; g.C = (float*)((char*)ck + layer); g.C2 = (float*)((char*)cv + layer);
-        g.c_rows_per_batch = rows; g.kv_heads = e->H; g.kv_cap = e->S; g.kv_seq_off = seq_off;
+        const size_t layer = (size_t)i * layer_rows * row_bytes;
+        GemmParams g = cross_kv_gemm_params(A, e->S, l.ckv_w, l.ckv_b, (char*)ck + layer, (char*)cv + layer, kv_esz, B, rows, e->H, e->S, seq_off, row0);
         if (e->w_half) {
             hipEvent_t ta, tb;
             timer_begin(e, e->t_gemm, s, &ta, &tb);
             LAUNCH(launch_gemm_f16(g, kv_esz == 2, s));
             timer_end(e, e->t_gemm, s, ta, tb);
         } else if (x3) {
-            g.A = (const float*)e->enc3; g.a_plane = (long long)enc_plane; g.W = (const float*)l.ckv_w3; g.w_plane = 2ll * d * d;
+            cross_kv_x3(g, e->enc3, enc_plane, l.ckv_w3);
             hipEvent_t ta, tb;
             timer_begin(e, e->t_gemm, s, &ta, &tb);
             LAUNCH(launch_gemm_x3(g, s));

@@ -15,7 +15,7 @@ namespace wt {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// fp32 -> three bf16 planes: b1 = rn(x), b2 = rn(x - b1), b3 = rn(x - b1 - b2); x = b1 + b2 + b3 to 2^-27 relative (wt_common.h: launch_gemm_x3)
+// fp32 -> three bf16 planes: b1 = rn(x), b2 = rn(x - b1), b3 = rn(x - b1 - b2); x = b1 + b2 + b3 to 2^-24 relative or better (wt_common.h: launch_gemm_x3)
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void split3(const float x, __bf16& b1, __bf16& b2, __bf16& b3) {
@@ -872,7 +872,7 @@ bool gemm_x3_usable(const GemmParams& p) {
     return a_span < (1ll << 32) && (long long)p.N * p.K * 2 < (1ll << 32) && p.a_batch_stride >= 0 && p.lda >= 0;
 }
 
-hipError_t launch_gemm_x3(const GemmParams& p_in, hipStream_t s) {
+hipError_t launch_gemm_x3(const GemmParams& p_in, hipStream_t s, int force_tile_arg) {
     GemmParams p = p_in;
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return hipSuccess;
     if (!gemm_x3_usable(p)) return hipErrorInvalidValue;
@@ -889,11 +889,12 @@ hipError_t launch_gemm_x3(const GemmParams& p_in, hipStream_t s) {
     // (256 slots), about twice as efficient per flop.  Estimated time = rounds of the chip x work per tile / efficiency; A/B:
     // WT_GEMM_X3_TILE=128|192|256
     static const int force_tile = tuning_env("WT_GEMM_X3_TILE") ? atoi(tuning_env("WT_GEMM_X3_TILE")) : 0;
+    if (force_tile_arg && force_tile_arg != 128 && force_tile_arg != 192 && force_tile_arg != 256) return hipErrorInvalidValue;
     const long long t128 = (long long)((p.N + 127) / 128) * ((p.M + 127) / 128), t256 = (long long)((p.N + 255) / 256) * ((p.M + 255) / 256),
                     t192 = (long long)((p.N + 255) / 256) * ((p.M + 191) / 192);
     // measured per round of the chip at K = 1024, M = 12000 (tools/microbench.py gemm_x3): 256x256 157 us, 192x256 142 us, 128x128 109 us
     const double cost256 = (double)((t256 + 255) / 256) * 1.0, cost192 = (double)((t192 + 255) / 256) * 0.905, cost128 = (double)((t128 + 511) / 512) * 0.695;
-    int tile = force_tile;
+    int tile = force_tile_arg ? force_tile_arg : force_tile;
     if (tile != 128 && tile != 192 && tile != 256) tile = (p.M < 192 || p.N < 256) ? 128 : (cost256 <= cost192 && cost256 <= cost128) ? 256 : cost192 <= cost128 ? 192 : 128;
     if (tile == 256) hipLaunchKernelGGL((gemm_x3_kernel<4, 4>), dim3((unsigned)t256), dim3(512), 0, s, p);
     else if (tile == 192) hipLaunchKernelGGL((gemm_x3_kernel<3, 4>), dim3((unsigned)t192), dim3(512), 0, s, p);

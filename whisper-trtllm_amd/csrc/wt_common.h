@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <atomic>
 
@@ -178,11 +179,16 @@ hipError_t launch_mel_transpose_split(const float* mel, void* planes, size_t pla
 hipError_t launch_layernorm(const float* x, const float* w, const float* b, float* y, int rows, int d, hipStream_t s);
 hipError_t launch_gemm_f32(const GemmParams& p, hipStream_t s);
 // ---- fp32 GEMM on the bf16 matrix cores.  x = b1 + b2 + b3 with bf16 b1 = rn(x), b2 = rn(x - b1), b3 = rn(x - b1 - b2) represents an fp32
-// value to 2^-27 relative (three 8-bit significands cover fp32's 24 bits; bf16 has fp32's exponent range), and a product a.w is the sum of
-// the six partial products a_i.w_j with i + j <= 4 up to 3 x 2^-27 relative -- below the 2^-24 rounding of an fp32 FMA.  Every partial
-// product of two bf16 values is exact in the MFMA's fp32 accumulator, which accumulates as the fp32 MFMA does.  Six
+// value to 2^-24 relative or better (three 8-bit significands cover fp32's 24 bits; bf16 has fp32's exponent range), with |b2| <= 2^-8 |x|
+// and |b3| <= 2^-16 |x|.  A product a.w is the sum of the six partial products a_i.w_j with i + j <= 4; the three dropped ones (a2.w3,
+// a3.w2, a3.w3) are each up to 2^-24 |a||w| in the worst case, about 2^-23 |a||w| per product together -- the size of the rounding of
+// an fp32 FMA, and measured no worse than the fp32 MFMA on random operands (tests/test_gpu_kernels.py::test_gemm_x3_is_an_fp32_gemm).
+// On a coherently growing sum (products of one sign) the accumulation error grows faster with K than the fp32 MFMA's: 3.7e-6 against
+// 4.2e-7 of sum |a||w| at K = 4096 (same test; the mechanism is not established).
+// Every partial product of two bf16 values is exact in the MFMA's fp32 accumulator, which accumulates as the fp32 MFMA does.  Six
 // v_mfma_f32_32x32x16_bf16 replace sixteen v_mfma_f32_32x32x2_f32 per 32x32x16 block: 16 / 6 = 2.7x the fp32 MFMA peak.
-hipError_t launch_gemm_x3(const GemmParams& p, hipStream_t s);
+// force_tile: 128 / 192 / 256 selects that tile instantiation (tests); 0 = by shape (or WT_GEMM_X3_TILE under WT_TUNING=1).
+hipError_t launch_gemm_x3(const GemmParams& p, hipStream_t s, int force_tile = 0);
 bool gemm_x3_usable(const GemmParams& p);   // shape / alignment limits of launch_gemm_x3 (else: launch_gemm_f32 on the fp32 operands)
 hipError_t launch_split3(const float* x, void* planes, size_t n, size_t plane_stride, hipStream_t s);   // fp32 [n] -> three bf16 planes
 hipError_t launch_layernorm_split(const float* x, const float* w, const float* b, void* planes, size_t plane_stride, int rows, int d, hipStream_t s);
@@ -245,6 +251,62 @@ hipError_t launch_stream_publish(const SelectParams& p, const StreamPublish& pub
 hipError_t launch_copy_cache_rows(const float* src, float* dst, int LH, int src_rows, int dst_rows, int n_rows,
                                   hipStream_t s);
 hipError_t launch_set_state(DecState* st, int cur_len, int pos, int self_len, hipStream_t s);
+
+// ---- GemmParams of the encoder's two convolutions and of the cross-K/V projection.  engine.hip and the debug hooks (debug_api.hip) both
+// build their launches here, so a test of a hook is a test of what the engine launches.
+// Conv workspace (per utterance b of B, Fr = 2 S frames): melT [B][Fr + 2][C] and c1 [B][Fr + 2][d], row t + 1 = frame t, rows 0 and
+// Fr + 1 the convolutions' zero padding, then 4 rows of slack; conv_ws_elems gives their elements.  CONV_X3 keeps both as three bf16 planes
+// (plane p at + p * elements), CONV_F16 as IEEE half, CONV_F32 as float.  conv1 (k 3, pad 1, GELU) reads melT and writes c1's rows 1..Fr;
+// conv2 (k 3, stride 2, pad 1, GELU, + pos) reads c1 with lda = 2d and writes out [B][S][d] (float).
+enum { CONV_F32 = 0, CONV_X3 = 1, CONV_F16 = 2 };
+inline void conv_ws_elems(int B, int S, int C, int d, size_t& n_melT, size_t& n_c1) {
+    const size_t rows = (size_t)B * (2 * (size_t)S + 2);
+    n_melT = rows * C + 4 * (size_t)C;
+    n_c1 = rows * d + 4 * (size_t)d;
+}
+// zero melT and c1 (their pad rows are never written by the kernels); esz: bytes per element of the whole buffer (4 fp32 -- the fp16
+// engines clear their half data in the same fp32-sized region --, 6 for three bf16 planes)
+inline hipError_t conv_ws_clear(void* melT, size_t n_melT, void* c1, size_t n_c1, size_t esz, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(melT, 0, n_melT * esz, s);
+    return e == hipSuccess ? hipMemsetAsync(c1, 0, n_c1 * esz, s) : e;
+}
+// w1 / w2: conv weights as the converter lays them out ([d][3 C] / [d][3 d], builder._conv_as_gemm): float, half, or plane 0 of three bf16 planes
+inline void conv_gemm_params(int mode, const void* melT, size_t n_melT, void* c1, size_t n_c1, const void* w1, const float* b1, const void* w2,
+                             const float* b2, const float* pos, float* out, int B, int S, int C, int d, GemmParams& c1g, GemmParams& c2g) {
+    const int Fr = 2 * S;
+    const size_t esz = mode == CONV_F32 ? 4 : 2;
+    memset(&c1g, 0, sizeof c1g);
+    c1g.A = (const float*)melT; c1g.lda = C; c1g.a_rows_per_batch = Fr; c1g.a_batch_stride = (long long)(Fr + 2) * C;
+    c1g.W = (const float*)w1; c1g.bias = b1; c1g.M = B * Fr; c1g.N = d; c1g.K = 3 * C; c1g.act = 1;
+    c1g.C = (float*)((char*)c1 + (size_t)d * esz); c1g.ldc = d; c1g.c_rows_per_batch = Fr; c1g.c_batch_stride = (long long)(Fr + 2) * d;
+    memset(&c2g, 0, sizeof c2g);
+    c2g.A = (const float*)c1; c2g.lda = 2 * d; c2g.a_rows_per_batch = S; c2g.a_batch_stride = (long long)(Fr + 2) * d;
+    c2g.W = (const float*)w2; c2g.bias = b2; c2g.M = B * S; c2g.N = d; c2g.K = 3 * d; c2g.act = 1; c2g.pos = pos;
+    c2g.C = out; c2g.ldc = d; c2g.c_rows_per_batch = S; c2g.c_batch_stride = (long long)S * d;
+    if (mode == CONV_X3) {   // conv1's GELU output goes out as planes for conv2
+        c1g.a_plane = (long long)n_melT; c1g.w_plane = (long long)d * 3 * C; c1g.out_split = 1; c1g.c_plane = (long long)n_c1;
+        c2g.a_plane = (long long)n_c1; c2g.w_plane = (long long)d * 3 * d;
+    }
+}
+// Cross-K/V projection of ONE decoder layer: encoder rows [0, rows) of each of B utterances (A [B][rows_total][d], float or half) times
+// W [2d][d] into the head-split caches [layer_rows][H][cap][64] of that layer (ck / cv: the layer's base), utterance b at cache row
+// row0 + b, sequence rows [seq_off, seq_off + rows); kv_esz bytes per cache element.  The x3 form: cross_kv_x3 on top.
+inline GemmParams cross_kv_gemm_params(const void* A, int rows_total, const void* W, const float* bias, void* ck, void* cv, int kv_esz, int B,
+                                       int rows, int H, int cap, int seq_off, int row0) {
+    const int d = H * HEAD_DIM;
+    const size_t row_off = (size_t)row0 * H * cap * HEAD_DIM * kv_esz;
+    GemmParams g;
+    memset(&g, 0, sizeof g);
+    g.A = (const float*)A; g.lda = d; g.a_rows_per_batch = rows; g.a_batch_stride = (long long)rows_total * d;
+    g.W = (const float*)W; g.bias = bias; g.M = B * rows; g.N = 2 * d; g.K = d;
+    g.epi = EPI_KV_HEADS; g.C = (float*)((char*)ck + row_off); g.C2 = (float*)((char*)cv + row_off);
+    g.c_rows_per_batch = rows; g.kv_heads = H; g.kv_cap = cap; g.kv_seq_off = seq_off;
+    return g;
+}
+// A3: the encoder rows as three bf16 planes of a_plane elements each (split3 of A), W3: the layer's weights as three planes of 2 d^2
+inline void cross_kv_x3(GemmParams& g, const void* A3, size_t a_plane, const void* W3) {
+    g.A = (const float*)A3; g.a_plane = (long long)a_plane; g.W = (const float*)W3; g.w_plane = 2ll * g.K * g.K;
+}
 
 // GELU (erf form) of the encoder epilogues.  erff() is ~38 vector ALU instructions in two divergent branches, executed beside the other
 // workgroups' MFMAs: 10 % of a small.en fc1 launch, 4 % of medium.en's.  Branch-free form: erf(|x| / sqrt 2) = 1 - 2^Q(|x|), Q of degree 8
