@@ -49,7 +49,12 @@ def parse_arguments():
     parser.add_argument("--workers", type=int, default=2, help="fast path: engine pairs per GPU, each on its own stream and host thread")
     parser.add_argument("--dist-backend", type=str, default=None, help="nccl (= RCCL) | gloo; default: nccl when every rank has its own GPU")
     parser.add_argument("--dump_ids", type=str, default=None, help="rank 0 writes the fast-path token ids as JSON (tests)")
-    return parser.parse_args()
+    parser.add_argument("--return_timestamps", action="store_true", help="Whisper's timestamp mode: <|t|> tokens (t x 0.02 s) between "
+                        "segments; printed as [start --> end] text segments with a tokenizer, as ids with <|t|> marks otherwise")
+    args = parser.parse_args()
+    if args.return_timestamps and args.batching == "continuous":
+        parser.error("--return_timestamps needs a batch plan (--batching sorted | dataset): the continuous mode predicts no timestamps")
+    return args
 
 
 def trim_after_eos(row, eos, pad):
@@ -120,12 +125,12 @@ class WhisperDecoder:
                                           outputs["next_cross_keys"], outputs["next_cross_values"])
 
 
-def decode_with_sessions(whisperencoder, whisperdecoder, config, mel):
+def decode_with_sessions(whisperencoder, whisperdecoder, config, mel, return_timestamps=False):
     """One utterance through the reference's loop (run.py:266-284)."""
     encoder_outputs = whisperencoder(mel)
     input_ids = torch.Tensor([[config["decoder_start_token_id"]]]).to(dtype=torch.int32).cuda()
     return greedy_search(model=whisperdecoder, encoder_outputs=encoder_outputs, input_ids=input_ids,
-                         logits_processor=get_logits_processor(config, input_ids.shape[-1]),
+                         logits_processor=get_logits_processor(config, input_ids.shape[-1], return_timestamps),
                          stopping_criteria=get_stopping_criteria(config),
                          pad_token_id=config["pad_token_id"], eos_token_id=config["eos_token_id"])
 
@@ -176,7 +181,8 @@ if __name__ == "__main__":
                 rows = pipe.transcribe_continuous(torch.cat(mels[begin:end]), slots=8, chunk=8) if end > begin else []
                 indexed = list(zip(range(begin, end), [r.tolist() for r in rows]))
             else:
-                for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups])):
+                kw = [{"return_timestamps": True}] * len(groups) if args.return_timestamps else None
+                for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):
                     indexed += list(zip(g, ids.cpu().tolist()))
             torch.cuda.synchronize()
             elapsed = tensorrt_llm.sharding.max_over_ranks(time.time() - t0, dist)
@@ -192,7 +198,7 @@ if __name__ == "__main__":
         for _ in range(2):
             torch.cuda.synchronize()
             t0 = time.time()
-            ids = [decode_with_sessions(whisperencoder, whisperdecoder, config, m)[0].cpu().tolist() for m in mels]
+            ids = [decode_with_sessions(whisperencoder, whisperdecoder, config, m, args.return_timestamps)[0].cpu().tolist() for m in mels]
             torch.cuda.synchronize()
             results["session"] = (time.time() - t0, ids)
         print(f"Session path: {results['session'][0]:.3f} s for {len(mels)} x 30 s  ({30 * len(mels) / results['session'][0]:.1f} audio-s/s)")
@@ -209,6 +215,13 @@ if __name__ == "__main__":
         tok = tensorrt_llm.text.WhisperTokenDecoder.from_dir(args.whisper)
         for path, ids in zip(args.audio, next(iter(results.values()))[1]):
             print(f"{os.path.basename(path)}: {tok.decode(ids, skip_special_tokens=True)!r}")
+            if args.return_timestamps:
+                for seg in tok.offsets(ids):
+                    print(f"  [{seg['timestamp'][0]:6.2f} --> {seg['timestamp'][1]:6.2f}] {seg['text']}")
+    elif rank == 0 and args.return_timestamps:       # no tokenizer: ids with the timestamps written out
+        tb = tensorrt_llm.runtime.timestamp_rules(config)[1]
+        for i, ids in enumerate(next(iter(results.values()))[1][:4]):
+            print(f"utterance {i}:", " ".join(f"<|{(t - tb) * 0.02:.2f}|>" if t >= tb else str(t) for t in ids))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

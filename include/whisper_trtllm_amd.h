@@ -166,6 +166,29 @@ int wt_decoder_read_ids(wt_engine* dec, int32_t* ids_out, int ld, void* stream);
 int wt_decoder_greedy(wt_engine* dec, const float* enc_hidden, int batch, const wt_greedy_params* p,
                       int32_t* ids_out, int* out_len, void* stream);
 
+/* (9b) timestamp mode of the batch decode (wt_decoder_begin / _steps / _run / _greedy): Whisper predicts <|t|> tokens
+ * (timestamp_begin + i = i x 0.02 s) under one more logits processor after Suppress -> SuppressAtBegin -> Force, the rules of
+ * WhisperTimeStampLogitsProcessor (transformers generation/logits_process.py), per row at sequence length cur_len (prompt included):
+ *   1. <|notimestamps|> is always masked;
+ *   2. at cur_len == begin_index - 1 the token is timestamp_begin (<|0.00|>);
+ *   3. of the ids from begin_index on, a timestamp after a timestamp (or as the first one) is followed by text: [timestamp_begin, V)
+ *      masked; a timestamp after text by a timestamp or EOS: [0, eos_token_id) masked;
+ *   4. at cur_len == begin_index with max_initial_timestamp_index >= 0: ids above timestamp_begin + max_initial_timestamp_index masked;
+ *   5. if logsumexp(scores[timestamp_begin:]) > max(scores[:timestamp_begin]), every text id is masked;
+ * then the argmax (lowest index on ties, NaN-aware) and the usual pad / EOS / max_length bookkeeping.  The setting applies from the
+ * next wt_decoder_begin on this handle; t == NULL or t->enabled == 0 turns it off.  WT_E_INVALID unless 0 < timestamp_begin < V,
+ * 0 <= no_timestamps_token_id < timestamp_begin and begin_index >= 2; wt_decoder_begin refuses (WT_E_INVALID) a forced list that
+ * holds no_timestamps_token_id or a forced position >= begin_index - 1, and wt_decoder_stream_begin refuses (WT_E_UNSUPPORTED) while
+ * the mode is on.  The logits pass through HBM in this mode (one more launch per step than the fused greedy argmax). */
+typedef struct {
+    int32_t enabled;
+    int32_t no_timestamps_token_id;
+    int32_t timestamp_begin;               /* first timestamp id (<|0.00|>); ids >= it are timestamps */
+    int32_t begin_index;                   /* sequence length at which the first generated timestamp is followed (.en: 2) */
+    int32_t max_initial_timestamp_index;   /* < 0: no cap on the first timestamp */
+} wt_timestamp_params;
+int wt_decoder_set_timestamp_rules(wt_engine* dec, const wt_timestamp_params* t);
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

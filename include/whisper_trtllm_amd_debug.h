@@ -9,6 +9,8 @@
 #ifndef WHISPER_TRTLLM_AMD_DEBUG_H
 #define WHISPER_TRTLLM_AMD_DEBUG_H
 #include <stddef.h>
+
+#include "whisper_trtllm_amd.h"   /* wt_timestamp_params */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -109,6 +111,15 @@ int wt_dbg_encoder_convs(const float* mel, const void* conv1_w, const float* con
  * then W's planes at the next multiple of 256 bytes, 12 (H*64)^2 bytes); tile as wt_dbg_gemm_x3_tile. */
 int wt_dbg_cross_kv(const float* A, int rows_total, const float* W, const float* bias, float* kcache, float* vcache, void* scratch, int B, int rows,
                     int H, int cap, int seq_off, int layer_rows, int row0, int mode, int tile, void* stream);
+
+/* the timestamp mode's two launches (ts_select_kernel + greedy_finish_kernel<true>, exactly as the engine enqueues them) on crafted
+ * rows: logits f32 [B][V] (B <= 16), ids int32 [B][max_length] (the row's history; position cur_len[0] is overwritten), cur_len a HOST
+ * array [B] with 1 <= cur_len[b] < max_length, t / eos as in wt_timestamp_params / wt_greedy_params (no suppress masks, no forced ids).
+ * tok_out int32 [B]: the chosen token; stats_out f32 [B][2]: (logsumexp of the masked timestamp scores, masked text maximum).
+ * scratch: wt_dbg_timestamp_select_scratch_bytes(B, V, max_length) bytes.  Synchronises `stream` (the state upload). */
+size_t wt_dbg_timestamp_select_scratch_bytes(int B, int V, int max_length);
+int wt_dbg_timestamp_select(const float* logits, int B, int V, int32_t* ids, int max_length, const int32_t* cur_len,
+                            const wt_timestamp_params* t, int eos, int32_t* tok_out, float* stats_out, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

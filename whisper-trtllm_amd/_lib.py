@@ -17,14 +17,15 @@ ABI_VERSION = 3
 EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
-    "wt_decoder_greedy", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
     "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_last_error", "wt_abi_version",
 ]
 DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_gemm_f16", "wt_dbg_gemm_f16_variant", "wt_dbg_layernorm", "wt_dbg_encoder_attention", "wt_dbg_encoder_attention_split", "wt_dbg_encoder_attention_x3", "wt_dbg_encoder_attention_f16", "wt_dbg_skinny", "wt_dbg_skinny_gelu_in", "wt_dbg_encoder_attention_occupancy", "wt_dbg_decode_attention",
                  "wt_dbg_decode_attention_folded", "wt_dbg_skinny_pair", "wt_dbg_attention_then_projection", "wt_dbg_self_attention_then_pair",
                  "wt_dbg_skinny_f16", "wt_dbg_decode_attention_f16", "wt_dbg_attention_then_projection_f16", "wt_dbg_skinny_pair_f16", "wt_dbg_gemm_f16_kv",
-                 "wt_dbg_gemm_x3_tile", "wt_dbg_layernorm_split", "wt_dbg_encoder_convs_scratch_bytes", "wt_dbg_encoder_convs", "wt_dbg_cross_kv"]
+                 "wt_dbg_gemm_x3_tile", "wt_dbg_layernorm_split", "wt_dbg_encoder_convs_scratch_bytes", "wt_dbg_encoder_convs", "wt_dbg_cross_kv",
+                 "wt_dbg_timestamp_select_scratch_bytes", "wt_dbg_timestamp_select"]
 
 
 class TensorDesc(Structure):
@@ -47,6 +48,10 @@ class GreedyParams(Structure):
                 ("begin_suppress_tokens", POINTER(c_int32)), ("n_begin_suppress_tokens", c_int32),
                 ("forced_decoder_ids", POINTER(c_int32)), ("n_forced", c_int32),
                 ("force_eos_step", c_int32), ("logits_trace", c_void_p), ("force_eos_steps", POINTER(c_int32))]
+
+
+class TimestampParams(Structure):
+    _fields_ = [(n, c_int32) for n in ("enabled", "no_timestamps_token_id", "timestamp_begin", "begin_index", "max_initial_timestamp_index")]
 
 
 class KernelTimer(Structure):
@@ -94,6 +99,7 @@ def load():
     lib.wt_decoder_run.argtypes = [c_void_p, c_int, POINTER(c_int), POINTER(c_int), c_void_p]
     lib.wt_decoder_read_ids.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.wt_decoder_greedy.argtypes = [c_void_p, c_void_p, c_int, POINTER(GreedyParams), c_void_p, POINTER(c_int), c_void_p]
+    lib.wt_decoder_set_timestamp_rules.argtypes = [c_void_p, POINTER(TimestampParams)]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -135,6 +141,9 @@ def load():
     lib.wt_dbg_encoder_convs_scratch_bytes.restype = c_size_t
     lib.wt_dbg_encoder_convs.argtypes = [P, P, P, P, P, P, P, P, I, I, I, I, I, I, P]
     lib.wt_dbg_cross_kv.argtypes = [P, I, P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]
+    lib.wt_dbg_timestamp_select_scratch_bytes.argtypes = [I, I, I]
+    lib.wt_dbg_timestamp_select_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_timestamp_select.argtypes = [P, I, I, P, I, POINTER(c_int32), POINTER(TimestampParams), I, P, P, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

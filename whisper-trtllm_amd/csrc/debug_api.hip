@@ -289,3 +289,52 @@ extern "C" int wt_dbg_gemm_f16_kv(const void* A, int rows_total, const void* W, 
     g.epi = EPI_KV_HEADS; g.C = (float*)kcache; g.C2 = (float*)vcache; g.c_rows_per_batch = rows; g.kv_heads = H; g.kv_cap = kv_cap; g.kv_seq_off = seq_off;
     return rc_of(launch_gemm_f16(g, out_half != 0, (hipStream_t)stream));
 }
+
+// ---- timestamp mode: the engine's two launches (launch_greedy_select with ts_on) over crafted logits and histories ----
+struct TsScratch { size_t st, unf, mask, forced, part, total; };
+static TsScratch ts_scratch_layout(int B, int V, int max_length) {
+    TsScratch l;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    l.st = take(sizeof(DecState)); l.unf = take((size_t)B * 4); l.mask = take((size_t)V); l.forced = take((size_t)(max_length + 1) * 4);
+    l.part = take((size_t)B * SELECT_CHUNKS * sizeof(TsPart));
+    l.total = off;
+    return l;
+}
+extern "C" size_t wt_dbg_timestamp_select_scratch_bytes(int B, int V, int max_length) {
+    if (B < 1 || V < 1 || max_length < 2) return 0;
+    return ts_scratch_layout(B, V, max_length).total;
+}
+extern "C" int wt_dbg_timestamp_select(const float* logits, int B, int V, int32_t* ids, int max_length, const int32_t* cur_len,
+                                       const wt_timestamp_params* t, int eos, int32_t* tok_out, float* stats_out, void* scratch, void* stream) {
+    if (!logits || !ids || !cur_len || !t || !tok_out || !stats_out || !scratch || B < 1 || B > MAX_ROWS || V < 1 || max_length < 2) return -22;
+    for (int b = 0; b < B; ++b)
+        if (cur_len[b] < 1 || cur_len[b] >= max_length) return -22;
+    if (eos < 0 || eos >= V) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    const TsScratch l = ts_scratch_layout(B, V, max_length);
+    char* base = (char*)scratch;
+    DecState h;
+    memset(&h, 0, sizeof h);
+    for (int b = 0; b < B; ++b) {
+        h.cur_len[b] = cur_len[b];
+        h.pos[b] = cur_len[b] - 1;
+        h.self_len[b] = cur_len[b] - 1;
+    }
+    int unf[MAX_ROWS];
+    for (int b = 0; b < MAX_ROWS; ++b) unf[b] = 1;
+    int rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.st, &h, sizeof h, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.unf, unf, (size_t)B * 4, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemsetAsync(base + l.mask, 0, (size_t)V, s)))) return rc;
+    if ((rc = rc_of(hipMemsetAsync(base + l.forced, 0xff, (size_t)(max_length + 1) * 4, s)))) return rc;   // -1: nothing forced
+    if ((rc = rc_of(hipStreamSynchronize(s)))) return rc;   // pageable sources
+    SelectParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.mask = (const uint8_t*)(base + l.mask); p.forced = (const int*)(base + l.forced); p.ids = ids;
+    p.unfinished = (int*)(base + l.unf); p.st = (DecState*)(base + l.st);
+    p.n_parts = SELECT_CHUNKS; p.B = B; p.V = V; p.max_length = max_length; p.begin_index = -1; p.eos = eos; p.pad = eos; p.force_eos_step = -1;
+    p.ts_on = 1; p.no_ts = t->no_timestamps_token_id; p.tb = t->timestamp_begin; p.ts_begin_index = t->begin_index;
+    p.max_init = t->max_initial_timestamp_index; p.ts_part = (TsPart*)(base + l.part); p.ts_tok = tok_out; p.ts_stats = stats_out;
+    return rc_of(launch_greedy_select(p, s));
+}

@@ -142,6 +142,10 @@ struct wt_engine {
     bool begun = false;
     int B = 0, max_length = 0, begin_index = 0, eos = 0, pad = 0, force_eos_step = -1, nsplit_self = 1, nsplit_cross = 4, start_token = 0;
     float* trace = nullptr;
+    // timestamp mode: the rules wt_decoder_set_timestamp_rules asked for (applied by the next wt_decoder_begin) and those of the
+    // decode in flight (enabled == 0: off)
+    wt_timestamp_params ts_req = {0, 0, 0, 0, 0}, ts_cur = {0, 0, 0, 0, 0};
+    TsPart* ts_part = nullptr;    // scratch [dec_cap][SELECT_CHUNKS] of ts_select_kernel
     hipStream_t own_stream = nullptr;
     // step graphs: [0] every row attends (the only one a decode without early finishers ever replays), [1] finished rows stream no K/V,
     // [2] / [3] the same two for the continuous mode (per-slot cross-cache rows, stream_finish_kernel)
@@ -657,13 +661,14 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     const size_t o_part = take((size_t)B * e->H * 16 * PART_STRIDE * 4), o_lg = take((size_t)B * e->V * 4);
     const size_t o_st = take(sizeof(DecState)), o_ids = take((size_t)B * cap_len * 4), o_unf = take((size_t)B * 4);
     const size_t o_forced = take((size_t)(cap_len + 1) * 4), o_mask = take((size_t)e->V), o_frows = take(16 * 4);
+    const size_t o_tsp = take((size_t)B * SELECT_CHUNKS * sizeof(TsPart));
     hipError_t he = hipMalloc((void**)&e->dec_ws, off);
     if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for decoder workspace (batch %d) failed: %s", off, B, hipGetErrorString(he));
     char* b = e->dec_ws;
     e->self_k = (float*)(b + o_sk); e->self_v = (float*)(b + o_sv); e->cross_k = (float*)(b + o_ck); e->cross_v = (float*)(b + o_cv);
     e->dh = (float*)(b + o_h); e->dh2 = (float*)(b + o_h2); e->dq = (float*)(b + o_q); e->datt = (float*)(b + o_att); e->att_cnt = (int*)(b + o_cnt); e->sel_val = (float*)(b + o_selv); e->sel_idx = (int*)(b + o_seli); e->dffn = (float*)(b + o_f); e->part = (float*)(b + o_part);
     e->logits = (float*)(b + o_lg); e->st = (DecState*)(b + o_st); e->ids = (int*)(b + o_ids); e->unfinished = (int*)(b + o_unf);
-    e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows);
+    e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows); e->ts_part = (TsPart*)(b + o_tsp);
     e->h_force_rows.clear();
     e->enc_h = e->w_half ? (void*)(b + o_ench) : nullptr;
     e->enc3 = e->use_x3 ? (void*)(b + o_enc3) : nullptr;
@@ -892,10 +897,14 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
         if (!tok_ok(p->begin_suppress_tokens[i])) return fail(WT_E_INVALID, "begin-suppress token %d outside the vocabulary", p->begin_suppress_tokens[i]);
         mask[p->begin_suppress_tokens[i]] |= 2;
     }
+    const wt_timestamp_params ts = stream_mode || !e->ts_req.enabled ? wt_timestamp_params{0, 0, 0, 0, 0} : e->ts_req;
     std::vector<int> forced(e->dec_maxlen_cap + 1, -1);
     for (int i = 0; i < p->n_forced; ++i) {
         const int idx = p->forced_decoder_ids[2 * i], tok = p->forced_decoder_ids[2 * i + 1];
         if (!tok_ok(tok)) return fail(WT_E_INVALID, "forced token %d outside the vocabulary", tok);
+        if (ts.enabled && (tok == ts.no_timestamps_token_id || idx >= ts.begin_index - 1))   // Force and Timestamp must not fight
+            return fail(WT_E_INVALID, "timestamp mode: forced token %d at %d (no <|notimestamps|>, no forced position >= begin_index - 1 = %d)",
+                        tok, idx, ts.begin_index - 1);
         if (idx >= 0 && idx <= e->dec_maxlen_cap) forced[idx] = tok;
     }
     if (!e->tables_valid || mask != e->h_mask || forced != e->h_forced) {
@@ -921,8 +930,10 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
     }
     const bool same = e->begun && e->B == B && e->max_length == p->max_length && e->trace == p->logits_trace &&
                       e->begin_index == p->begin_index && e->eos == p->eos_token_id && e->pad == p->pad_token_id &&
-                      e->force_eos_step == p->force_eos_step && e->start_token == p->decoder_start_token_id;
+                      e->force_eos_step == p->force_eos_step && e->start_token == p->decoder_start_token_id &&
+                      memcmp(&e->ts_cur, &ts, sizeof ts) == 0;
     if (!same) e->graph_valid = false;
+    e->ts_cur = ts;
     e->B = B; e->max_length = p->max_length; e->begin_index = p->begin_index; e->eos = p->eos_token_id;
     e->pad = p->pad_token_id; e->force_eos_step = p->force_eos_step; e->trace = p->logits_trace; e->start_token = p->decoder_start_token_id;
     // measured (tools/microbench.py, medium.en B=8): self attention is fastest unsplit at every length <= 448;
@@ -954,6 +965,22 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_timestamp_rules(wt_engine* e, const wt_timestamp_params* t) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: not a decoder engine");
+    if (!t || !t->enabled) {
+        e->ts_req = wt_timestamp_params{0, 0, 0, 0, 0};
+        return WT_OK;
+    }
+    if (t->timestamp_begin <= 0 || t->timestamp_begin >= e->V)
+        return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: timestamp_begin %d outside (0, V=%d)", t->timestamp_begin, e->V);
+    if (t->no_timestamps_token_id < 0 || t->no_timestamps_token_id >= t->timestamp_begin)
+        return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: no_timestamps_token_id %d outside [0, timestamp_begin=%d)", t->no_timestamps_token_id, t->timestamp_begin);
+    if (t->begin_index < 2) return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: begin_index %d < 2 (the prompt holds the start token)", t->begin_index);
+    e->ts_req = *t;
+    e->ts_req.enabled = 1;
+    return WT_OK;
+}
+
 extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, const wt_greedy_params* p, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_begin: not a decoder engine");
     if (!enc_hidden || !p || B < 1) return fail(WT_E_INVALID, "wt_decoder_begin: bad arguments");
@@ -979,6 +1006,10 @@ static void fill_select_params(wt_engine* e, SelectParams& sp) {
     sp.d_model = e->d; sp.n_parts = 8; sp.fused = 0; sp.emb_half = e->w_half;
     sp.force_eos_rows = e->force_rows_on ? e->force_rows : nullptr; sp.mailbox = e->mailbox_dev;
     sp.start_token = e->start_token;
+    if (e->ts_cur.enabled && !e->stream_mode) {
+        sp.ts_on = 1; sp.no_ts = e->ts_cur.no_timestamps_token_id; sp.tb = e->ts_cur.timestamp_begin;
+        sp.ts_begin_index = e->ts_cur.begin_index; sp.max_init = e->ts_cur.max_initial_timestamp_index; sp.ts_part = e->ts_part;
+    }
     if (e->stream_mode) {
         sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1; sp.force_eos_rows = nullptr; sp.trace = nullptr;
     }
@@ -996,12 +1027,13 @@ static int enqueue_fast_step(wt_engine* e, hipStream_t s, int variant = 0) {
     static const bool fuse = tuning_env("WT_NO_FUSED_ARGMAX") == nullptr;  // A/B switch: logits to HBM + greedy_select_kernel
     SelectParams sp;
     fill_select_params(e, sp);
+    const bool fused = fuse && !sp.ts_on;   // timestamp mode: plain logits to HBM, then ts_select_kernel
     int parts = 0;
-    io.argmax = fuse ? &sp : nullptr;
+    io.argmax = fused ? &sp : nullptr;
     io.argmax_parts = &parts;
     int rc = enqueue_step(e, io, s);
     if (rc) return rc;
-    if (fuse) { sp.fused = 1; sp.n_parts = parts; }
+    if (fused) { sp.fused = 1; sp.n_parts = parts; }
     LAUNCH(launch_greedy_select(sp, s));
     return WT_OK;
 }
@@ -1074,6 +1106,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     if (!p || slots < 1) return fail(WT_E_INVALID, "wt_decoder_stream_begin: bad arguments");
     if (pool_rows <= 0) pool_rows = 4 * slots;     // slots decoding + 3 x slots prepared ahead
     if (pool_rows < slots + 1 || pool_rows > STREAM_QCAP) return fail(WT_E_INVALID, "wt_decoder_stream_begin: pool of %d rows outside [slots + 1, %d]", pool_rows, STREAM_QCAP);
+    if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: timestamp mode is a batch-decode feature (wt_decoder_begin)");
     if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);

@@ -997,8 +997,6 @@ hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s) {
 //   greedy_select_kernel  grid (SELECT_CHUNKS, B): masked partial argmax of one vocabulary chunk (lowest index on ties);
 //   greedy_finish_kernel  one block: final argmax per row, forced / pad / EOS rules, append, advance the step counters,
 //                         stop test, and the NEXT step's input embedding (embed_tokens[tok] + embed_positions[pos]).
-constexpr int SELECT_CHUNKS = 8;
-
 __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p) {
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
@@ -1067,6 +1065,156 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
     }
 }
 
+// ---- timestamp mode (WhisperTimeStampLogitsProcessor, logits_process.py:1331-1396, after Suppress -> SuppressAtBegin -> Force).
+// ts_select_kernel, grid (SELECT_CHUNKS, B): the static masks, <|notimestamps|> and the per-row timestamp grammar (pairs; nothing but
+// a timestamp or EOS.. after a lone timestamp; the max-initial-timestamp cap), then one TsPart per chunk.  The log-sum-exp of the
+// timestamp scores against the text maximum (rule 5) and the forced <|0.00|> (rule 2) are decided by greedy_finish_kernel<true>.
+// (sum, max) pairs: s * exp(m - nm) with the empty pair (0, -inf) contributing 0 and a NaN sum staying NaN.
+__device__ __forceinline__ float ts_rescale(float s, float m, float nm) { return s == 0.f ? 0.f : s * expf(m - nm); }
+
+__global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
+    __shared__ TsPart s_part[4];
+    const DecState* st = p.st;
+    if (st->done) return;  // steps enqueued past the stop test are no-ops
+    const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
+    const bool at_begin = cur_len == p.begin_index;
+    const float* lg = p.logits + (size_t)b * p.V;
+    float* tr = p.trace ? p.trace + ((size_t)b * (p.max_length - 1) + step) * p.V : nullptr;
+    // the grammar of the row's timestamps so far (ids from ts_begin_index on) as two cut points: text ids below text_lo and
+    // timestamps above ts_hi are masked
+    const int* row = p.ids + (size_t)b * p.max_length;
+    const int n = cur_len - p.ts_begin_index;
+    const bool last = n >= 1 && row[cur_len - 1] >= p.tb;
+    const bool penult = n < 2 || row[cur_len - 2] >= p.tb;
+    int text_lo = 0, ts_hi = p.V - 1;
+    if (last && penult) ts_hi = p.tb - 1;      // two timestamps in a row: text next
+    if (last && !penult) text_lo = p.eos;      // a lone timestamp: its partner (or EOS and above) next
+    if (cur_len == p.ts_begin_index && p.max_init >= 0) ts_hi = min(ts_hi, p.tb + p.max_init);
+    TsPart r;
+    r.tmax = r.smax = r.zmax = -INFINITY;
+    r.targ = r.sarg = 0x7fffffff;
+    r.zsum = 0.f;
+    auto consider = [&](float x, uint8_t mk, int v) {
+        if ((mk & 1) || ((mk & 2) && at_begin) || v == p.no_ts || v < text_lo || v > ts_hi) x = -INFINITY;
+        if (v < p.tb) {
+            if (argmax_better(x, v, r.tmax, r.targ)) {
+                r.tmax = x;
+                r.targ = v;
+            }
+        } else {
+            if (argmax_better(x, v, r.smax, r.sarg)) {
+                r.smax = x;
+                r.sarg = v;
+            }
+            if (x > r.zmax) {
+                r.zsum = ts_rescale(r.zsum, r.zmax, x) + 1.f;
+                r.zmax = x;
+            } else if (x != -INFINITY) {
+                r.zsum += expf(x - r.zmax);   // (NaN x: the sum becomes NaN)
+            }
+        }
+    };
+    if ((p.V & 3) == 0) {  // 16-byte path, as greedy_select_kernel
+        const int n4 = p.V >> 2, per = (n4 + SELECT_CHUNKS - 1) / SELECT_CHUNKS;
+        const int i0 = chunk * per, i1 = min(n4, i0 + per);
+        const float4* lg4 = reinterpret_cast<const float4*>(lg);
+        const uchar4* mk4 = reinterpret_cast<const uchar4*>(p.mask);
+        float4* tr4 = reinterpret_cast<float4*>(tr);
+#pragma unroll 4
+        for (int i = i0 + tid; i < i1; i += 256) {
+            const float4 x = lg4[i];
+            const uchar4 m = mk4[i];
+            if (tr) tr4[i] = x;
+            consider(x.x, m.x, 4 * i);
+            consider(x.y, m.y, 4 * i + 1);
+            consider(x.z, m.z, 4 * i + 2);
+            consider(x.w, m.w, 4 * i + 3);
+        }
+    } else {
+        const int per = (p.V + SELECT_CHUNKS - 1) / SELECT_CHUNKS;
+        const int v0 = chunk * per, v1 = min(p.V, v0 + per);
+        for (int v = v0 + tid; v < v1; v += 256) {
+            const float x = lg[v];
+            if (tr) tr[v] = x;
+            consider(x, p.mask[v], v);
+        }
+    }
+    auto merge = [](TsPart& a, const TsPart& o) {
+        if (argmax_better(o.tmax, o.targ, a.tmax, a.targ)) {
+            a.tmax = o.tmax;
+            a.targ = o.targ;
+        }
+        if (argmax_better(o.smax, o.sarg, a.smax, a.sarg)) {
+            a.smax = o.smax;
+            a.sarg = o.sarg;
+        }
+        const float nm = fmaxf(a.zmax, o.zmax);   // (never NaN: zmax only takes finite or infinite scores)
+        a.zsum = ts_rescale(a.zsum, a.zmax, nm) + ts_rescale(o.zsum, o.zmax, nm);
+        a.zmax = nm;
+    };
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        TsPart x;
+        x.tmax = __shfl_xor(r.tmax, o);
+        x.targ = __shfl_xor(r.targ, o);
+        x.smax = __shfl_xor(r.smax, o);
+        x.sarg = __shfl_xor(r.sarg, o);
+        x.zmax = __shfl_xor(r.zmax, o);
+        x.zsum = __shfl_xor(r.zsum, o);
+        merge(r, x);
+    }
+    if ((tid & 63) == 0) s_part[tid >> 6] = r;
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < 4; ++i) merge(r, s_part[i]);
+        p.ts_part[b * SELECT_CHUNKS + chunk] = r;
+    }
+}
+
+// greedy_finish_kernel<true>: the SELECT_CHUNKS partials of a row sit in the first lanes of its lane group (requested before the
+// DecState is read, like finish_request)
+__device__ __forceinline__ void ts_request(const SelectParams& p, const int b, const int l, TsPart& c) {
+    c = p.ts_part[(size_t)min(b, p.B - 1) * SELECT_CHUNKS + min(l, SELECT_CHUNKS - 1)];
+}
+// rules 2 and 5 and the argmax of one row; every lane of the group returns the same token
+__device__ __forceinline__ int ts_pick(const SelectParams& p, const int b, const int l, const int lpb, const TsPart& c, const int cur_len) {
+    float tm = -INFINITY, sm = -INFINITY, zm = -INFINITY, zs = 0.f;
+    int ti = 0x7fffffff, si = 0x7fffffff;
+    if (b < p.B && l < SELECT_CHUNKS) {
+        tm = c.tmax; ti = c.targ; sm = c.smax; si = c.sarg; zm = c.zmax; zs = c.zsum;
+    }
+    float M = zm;
+    for (int o = lpb >> 1; o >= 1; o >>= 1) {   // lpb <= 64 and a power of two: a group never straddles a wave
+        const float otm = __shfl_xor(tm, o), osm = __shfl_xor(sm, o);
+        const int oti = __shfl_xor(ti, o), osi = __shfl_xor(si, o);
+        if (argmax_better(otm, oti, tm, ti)) {
+            tm = otm;
+            ti = oti;
+        }
+        if (argmax_better(osm, osi, sm, si)) {
+            sm = osm;
+            si = osi;
+        }
+        M = fmaxf(M, __shfl_xor(M, o));
+    }
+    float Z = ts_rescale(zs, zm, M);
+    for (int o = lpb >> 1; o >= 1; o >>= 1) Z += __shfl_xor(Z, o);
+    const float lse = M + logf(Z);   // -inf when every timestamp is masked (M = -inf, Z = 0); NaN with a NaN timestamp score
+    int tok;
+    if (cur_len == p.ts_begin_index - 1) tok = p.tb;        // rule 2: <|0.00|> opens the transcript
+    else if (lse > tm) tok = si;                            // rule 5: the timestamps' total mass beats every text token
+    else tok = argmax_better(sm, si, tm, ti) ? si : ti;
+    if ((unsigned)tok >= (unsigned)p.V) tok = p.eos;        // unreachable with a NaN-aware argmax; never index the embedding out of range
+    if (b < p.B && l == 0) {
+        if (p.ts_tok) p.ts_tok[b] = tok;
+        if (p.ts_stats) {
+            p.ts_stats[2 * b] = lse;
+            p.ts_stats[2 * b + 1] = tm;
+        }
+    }
+    return tok;
+}
+
 // Final masked argmax of every row over its n_parts partial results (lowest index on ties), shared by the two finish kernels.  All rows
 // at once: a group of `lpb` lanes per row (64 at B <= 4, 32 at B <= 8, 16 at B <= 16), every load of the block in flight together -- the
 // partials were written by other XCDs a kernel ago, so this is one memory round trip; row by row it was B of them (measured 14 us per
@@ -1127,6 +1275,8 @@ __device__ __forceinline__ void finish_embed(const SelectParams& p, const int* s
     }
 }
 
+// TS: the timestamp mode's pick (ts_pick over ts_select_kernel's partials) instead of the plain argmax; the bookkeeping is shared
+template <bool TS>
 __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p) {
     __shared__ int s_tok[MAX_ROWS];
     __shared__ int s_pos[MAX_ROWS];
@@ -1136,7 +1286,9 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     const int lpb = p.B <= 4 ? 64 : p.B <= 8 ? 32 : 16;
     const int b = tid / lpb, l = tid % lpb, bc = min(b, p.B - 1);
     FinishCand cand;
-    finish_request(p, b, l, lpb, cand);
+    TsPart tcand;
+    if constexpr (TS) ts_request(p, b, l, tcand);
+    else finish_request(p, b, l, lpb, cand);
     const int unf = p.unfinished[bc];
     // the rows of a wt_decoder_begin batch stay aligned: row 0's counters are everybody's
     const int done = st->done, cur_len = st->cur_len[0], step = st->step, pos = st->pos[0], self_len = st->self_len[0], seq = st->seq + 1,
@@ -1152,7 +1304,9 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     }
     const int forced = p.forced[cur_len];                          // ForceTokensLogitsProcessor
     const int row_eos = p.force_eos_rows ? p.force_eos_rows[bc] : -1;
-    int tok = finish_argmax(p, b, l, lpb, cand);
+    int tok;
+    if constexpr (TS) tok = ts_pick(p, b, l, lpb, tcand, st->cur_len[bc]);
+    else tok = finish_argmax(p, b, l, lpb, cand);
     if (b < p.B && l == 0) {
         if (forced >= 0) tok = forced;
         if (p.force_eos_step >= 0 && step == p.force_eos_step) tok = p.eos;  // bench-only transcript length
@@ -1332,9 +1486,16 @@ hipError_t launch_stream_publish(const SelectParams& p, const StreamPublish& pub
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     if (p.B > MAX_ROWS || p.n_parts < 1 || (!p.fused && p.n_parts != SELECT_CHUNKS)) return hipErrorInvalidValue;
     if (p.stream && (!p.host_ids || !p.host_len || p.trace)) return hipErrorInvalidValue;
+    if (p.ts_on) {   // timestamp mode: batch decodes only, over logits in HBM
+        if (p.fused || p.stream || !p.ts_part || p.tb <= 0 || p.tb >= p.V || p.no_ts < 0 || p.no_ts >= p.tb || p.ts_begin_index < 2)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ts_select_kernel, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(greedy_finish_kernel<true>, dim3(1), dim3(256), 0, s, p);
+        return hipGetLastError();
+    }
     if (!p.fused) hipLaunchKernelGGL(greedy_select_kernel, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);  // else: done by the vocabulary GEMV
     if (p.stream) hipLaunchKernelGGL(stream_finish_kernel, dim3(1), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(greedy_finish_kernel, dim3(1), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(greedy_finish_kernel<false>, dim3(1), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

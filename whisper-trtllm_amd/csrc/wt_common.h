@@ -213,6 +213,20 @@ int skinny_grid(const SkinnyParams& p);  // workgroups launch_skinny uses for p 
 hipError_t launch_skinny_pair(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s);
 hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s);
 
+constexpr int SELECT_CHUNKS = 8;   // vocabulary chunks (workgroups per row) of greedy_select_kernel / ts_select_kernel
+// Timestamp mode: one chunk's partial result per row (ts_select_kernel -> greedy_finish_kernel<true>).  Over the masked scores of the
+// chunk: the text maximum and its index over [0, tb), the timestamp maximum and its index over [tb, V) (both NaN-aware, lowest index on
+// ties), and the timestamp log-sum-exp as (zmax, zsum) = (largest finite timestamp score, sum of exp(x - zmax)); a NaN timestamp score
+// makes zsum NaN.
+struct TsPart {
+    float tmax;
+    int targ;
+    float smax;
+    int sarg;
+    float zmax, zsum;
+    int pad[2];
+};
+
 struct SelectParams {
     const float* logits;   // [B][V]
     const uint8_t* mask;   // [V] bit0: always suppressed, bit1: suppressed when cur_len == begin_index
@@ -236,6 +250,13 @@ struct SelectParams {
     int stream, start_token;
     int* host_ids;                   // device address of the pinned id rows [pool][max_length]
     int* host_len;                   // device address of the pinned final lengths [pool] (0 = still decoding)
+    // timestamp mode (ts_on != 0; wt_decoder_set_timestamp_rules): the logits reach HBM (fused == 0), ts_select_kernel + the timestamp
+    // instantiation of greedy_finish_kernel replace the plain argmax.  no_ts = <|notimestamps|>, tb = first timestamp id,
+    // ts_begin_index = sequence length of the first generated timestamp + 1, max_init < 0: no max-initial-timestamp rule
+    int ts_on, no_ts, tb, ts_begin_index, max_init;
+    TsPart* ts_part;                 // scratch [B][SELECT_CHUNKS]
+    int* ts_tok;                     // optional [B]: the rule-chosen token before the forced / pad / EOS bookkeeping (debug hook)
+    float* ts_stats;                 // optional [B][2]: (log-sum-exp of the timestamp scores, text maximum) after the masks (debug hook)
 };
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s);
 hipError_t launch_dec_init(DecState* st, int* ids, int* unfinished, int B, int max_length, int start_token, int epoch, hipStream_t s);

@@ -50,6 +50,39 @@ class ForceTokensLogitsProcessor:
         return scores
 
 
+class WhisperTimeStampLogitsProcessor:
+    """Timestamp rules (logits_process.py:1331-1396; the engine's ts_select_kernel / greedy_finish_kernel<true>).  `begin_index` is
+    the reference's `self.begin_index` (runtime.timestamp_rules: 2 for the .en models)."""
+
+    def __init__(self, eos_token_id, no_timestamps_token_id, begin_index, max_initial_timestamp_index=1):
+        self.eos_token_id, self.no_timestamps_token_id = eos_token_id, no_timestamps_token_id
+        self.timestamp_begin = no_timestamps_token_id + 1
+        self.begin_index, self.max_initial_timestamp_index = begin_index, max_initial_timestamp_index
+
+    def __call__(self, input_ids, scores):
+        tb = self.timestamp_begin
+        scores[:, self.no_timestamps_token_id] = -float("inf")
+        if input_ids.shape[1] == self.begin_index - 1:
+            scores[:, :] = -float("inf")
+            scores[:, tb] = 0
+            return scores
+        for k in range(input_ids.shape[0]):
+            seq = input_ids[k, self.begin_index:].tolist()
+            last = len(seq) >= 1 and seq[-1] >= tb
+            penult = len(seq) < 2 or seq[-2] >= tb
+            if last and penult:
+                scores[k, tb:] = -float("inf")
+            elif last:
+                scores[k, :self.eos_token_id] = -float("inf")
+        if input_ids.shape[1] == self.begin_index and self.max_initial_timestamp_index is not None and self.max_initial_timestamp_index >= 0:
+            scores[:, tb + self.max_initial_timestamp_index + 1:] = -float("inf")
+        logprobs = torch.nn.functional.log_softmax(scores.float(), dim=-1)
+        for k in range(input_ids.shape[0]):
+            if logprobs[k, tb:].logsumexp(dim=-1) > logprobs[k, :tb].max():
+                scores[k, :tb] = -float("inf")
+        return scores
+
+
 class MaxLengthCriteria:
     def __init__(self, max_length: int, max_position_embeddings: Optional[int] = None):
         self.max_length = max_length
@@ -63,14 +96,22 @@ class StoppingCriteriaList(list):
         return any(c(input_ids, scores) for c in self)
 
 
-def get_logits_processor(config: dict, input_ids_seq_length: int) -> LogitsProcessorList:
-    """run.py:150-162."""
+def get_logits_processor(config: dict, input_ids_seq_length: int, return_timestamps: bool = False) -> LogitsProcessorList:
+    """run.py:150-162; `return_timestamps`: the forced list loses <|notimestamps|> and the timestamp rules come last (the engine's
+    timestamp mode, runtime.timestamp_rules)."""
+    forced = config["forced_decoder_ids"]
+    if return_timestamps:
+        from .runtime import timestamp_rules
+        no_ts, _tb, ts_begin, max_init, forced = timestamp_rules(config)
     procs = LogitsProcessorList()
     procs.append(SuppressTokensLogitsProcessor(config["suppress_tokens"]))
     begin_index = input_ids_seq_length if config["forced_bos_token_id"] is None else input_ids_seq_length + 1
-    begin_index += config["forced_decoder_ids"][-1][0]
+    if forced:
+        begin_index += forced[-1][0]
     procs.append(SuppressTokensAtBeginLogitsProcessor(config["begin_suppress_tokens"], begin_index))
-    procs.append(ForceTokensLogitsProcessor(config["forced_decoder_ids"]))
+    procs.append(ForceTokensLogitsProcessor(forced))
+    if return_timestamps:
+        procs.append(WhisperTimeStampLogitsProcessor(config["eos_token_id"], no_ts, ts_begin, max_init))
     return procs
 
 

@@ -189,6 +189,26 @@ def _i32_array(values: Sequence[int]):
     return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
 
 
+def timestamp_rules(config: dict):
+    """Timestamp mode of a config (WhisperTimeStampLogitsProcessor's constants, logits_process.py:1350-1357): returns
+    (no_timestamps_token_id, timestamp_begin, ts_begin_index, max_initial_timestamp_index, forced list without <|notimestamps|>).
+    `ts_begin_index` is what the reference computes from the model's own forced list (.en: [[1, no_ts]] -> 2).  Raises ValueError for a
+    forced list the timestamp rule would fight with: a forced position >= ts_begin_index - 1 (the forced <|0.00|> step or later)."""
+    forced = [list(x) for x in (config.get("forced_decoder_ids") or [])]
+    no_ts = config.get("no_timestamps_token_id")
+    if no_ts is None:
+        if not forced:
+            raise ValueError("timestamp mode needs no_timestamps_token_id (or forced_decoder_ids ending in <|notimestamps|>)")
+        no_ts = forced[-1][1]
+    ts_begin = len(forced) + 2 - (1 if forced and forced[-1][1] == no_ts else 0)
+    kept = [pair for pair in forced if pair[1] != no_ts]
+    bad = [pair for pair in kept if pair[0] >= ts_begin - 1]
+    if bad:
+        raise ValueError(f"timestamp mode: forced ids {bad} at or after the forced <|0.00|> position {ts_begin - 1}")
+    max_init = config.get("max_initial_timestamp_index", 1)
+    return int(no_ts), int(no_ts) + 1, ts_begin, -1 if max_init is None else int(max_init), kept
+
+
 class WhisperDecoderEngine:
     """Greedy decode with the KV cache resident on the device (no per-token host round trip).
 
@@ -206,10 +226,12 @@ class WhisperDecoderEngine:
         """Another engine on the same device weights (own resident KV caches, step graphs, mailbox): for a second host thread / stream."""
         return WhisperDecoderEngine(None, self.config, _session=self.session.clone())
 
-    def _params(self, max_length, force_eos_step, logits_trace, force_eos_steps=None):
+    def _params(self, max_length, force_eos_step, logits_trace, force_eos_steps=None, return_timestamps=False):
         cfg = self.config
         begin_index = 1 if cfg.get("forced_bos_token_id") is None else 2          # run.py:155-156 with a 1-token prompt
         forced = cfg.get("forced_decoder_ids") or []
+        if return_timestamps:                     # the (1, <|notimestamps|>) pair leaves the prompt
+            forced = timestamp_rules(cfg)[4]
         if forced:
             begin_index += forced[-1][0]                                           # run.py:157
         p = _lib.GreedyParams()
@@ -233,7 +255,18 @@ class WhisperDecoderEngine:
             p.force_eos_steps = ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32))
         return p
 
-    def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None):
+    def _set_timestamp_rules(self, on: bool):
+        t = None
+        if on:
+            no_ts, tb, ts_begin, max_init, _forced = timestamp_rules(self.config)
+            t = _lib.TimestampParams(1, no_ts, tb, ts_begin, max_init)
+        _lib.check(self.session._lib.wt_decoder_set_timestamp_rules(self.session.handle, ctypes.byref(t) if t is not None else None),
+                   "wt_decoder_set_timestamp_rules")
+
+    def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
+              return_timestamps: bool = False):
+        """Start a decode (wt_decoder_begin).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
+        the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s)."""
         import torch
         i = self.session.info
         if encoder_hidden.dtype != torch.float32 or tuple(encoder_hidden.shape[1:]) != (i.max_source_positions, i.d_model):
@@ -244,8 +277,9 @@ class WhisperDecoderEngine:
         self._B = self._enc.shape[0]
         if force_eos_steps is not None and len(force_eos_steps) != self._B:
             raise ValueError(f"force_eos_steps needs one entry per utterance ({self._B}), got {len(force_eos_steps)}")
-        self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps)
+        self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps)
         self._trace = logits_trace
+        self._set_timestamp_rules(return_timestamps)
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.session._lib.wt_decoder_begin(self.session.handle, self._enc.data_ptr(), self._B, ctypes.byref(self._p),
                                                        ctypes.c_void_p(stream)), "wt_decoder_begin")
@@ -283,8 +317,9 @@ class WhisperDecoderEngine:
         return buf[:, :cur_len].clone()
 
     def generate(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, chunk: int = 0, force_eos_steps=None,
-                 lookahead: int = 0):
+                 lookahead: int = 0, return_timestamps: bool = False):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
+        `return_timestamps`: timestamp mode (see `begin`).
 
         Default (`chunk` 0): the stop test is followed through the engine's host mailbox (`run`), at most `lookahead` steps are
         enqueued past the stop.  `chunk` > 0 selects the older protocol -- `chunk` steps between two synchronising polls."""
@@ -295,13 +330,14 @@ class WhisperDecoderEngine:
             if logits_trace is not None:
                 raise ValueError(f"logits_trace supports at most {self.max_batch} utterances per call")
             parts = [self.generate(encoder_hidden[i:i + self.max_batch], max_length, force_eos_step, None, chunk,
-                                   None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead)
+                                   None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead,
+                                   return_timestamps)
                      for i in range(0, encoder_hidden.shape[0], self.max_batch)]
             width = max(p.shape[1] for p in parts)
             pad = self.config["pad_token_id"]
             parts = [torch.nn.functional.pad(p, (0, width - p.shape[1]), value=pad) for p in parts]
             return torch.cat(parts, dim=0)
-        self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps)
+        self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps)
         if chunk <= 0:
             cur, _nu = self.run(lookahead)
             return self.read_ids(cur)
@@ -312,9 +348,12 @@ class WhisperDecoderEngine:
             cur, _nu, done = self.poll()
         return self.read_ids(cur)
 
-    def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None) -> "DecodeStream":
+    def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False) -> "DecodeStream":
         """Open a continuous decode on this engine (wt_decoder_stream_*): `slots` rows stay busy, every utterance stops at its own EOS
-        and its slot is refilled on the device within the same step.  Ends with the next `begin` / `generate` on this engine."""
+        and its slot is refilled on the device within the same step.  Ends with the next `begin` / `generate` on this engine.
+        The continuous mode has no timestamp mode: `return_timestamps=True` raises ValueError."""
+        if return_timestamps:
+            raise ValueError("timestamp mode is a batch-decode feature (generate / begin); the continuous mode does not predict timestamps")
         return DecodeStream(self, slots, pool_rows, max_length)
 
     def set_profiling(self, enabled: bool):
@@ -362,6 +401,7 @@ class DecodeStream:
         self._lib, self._h = dec.session._lib, dec.session.handle
         self._p = dec._params(max_length, None, None)
         self.max_length = int(self._p.max_length)
+        dec._set_timestamp_rules(False)     # a timestamp decode before on this handle left the mode on
         self.pool_rows = int(pool_rows) if pool_rows else 4 * self.slots
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_decoder_stream_begin(self._h, self.slots, self.pool_rows, ctypes.byref(self._p), ctypes.c_void_p(stream)),
@@ -428,12 +468,14 @@ class DecodeStream:
 
 def transcribe_continuous(enc: "WhisperEncoderEngine", dec: "WhisperDecoderEngine", mels, slots: int = 8, chunk: int = 8,
                           force_eos_steps: Optional[Sequence[int]] = None, max_length=None, stats: Optional[dict] = None,
-                          pool_rows: int = 0) -> List[Any]:
+                          pool_rows: int = 0, return_timestamps: bool = False) -> List[Any]:
     """Encoder + continuous greedy decode of `mels` ([N, n_mels, 2*S] tensor or a list of such rows) in ARRIVAL order: the encoder runs
     on chunks of `chunk` utterances just ahead of the decode, `slots` rows decode at any time.  Returns N numpy id rows (start token
     through EOS) in input order.  This is the host scheduler of the C-ABI's continuous mode -- what cal_wer.py / run.py use for a
     dataset whose transcripts differ in length.  `stats` (optional dict) receives the slot utilisation of the run."""
     import torch
+    if return_timestamps:
+        raise ValueError("timestamp mode is a batch-decode feature (WhisperDecoderEngine.generate); the continuous mode does not predict timestamps")
     n = len(mels)
     results: List[Any] = [None] * n
     if n == 0:

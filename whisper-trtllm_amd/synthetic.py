@@ -59,6 +59,9 @@ CONFIGS = {
     "toy": _toy(),                                   # SURVEY §8(c) toy: full 1500-frame memory
     "toy-short": _toy(src=96, tgt=40, max_length=20),  # 192 mel frames, 96-frame memory
     "toy-wide": _toy(d_model=192, heads=3, ffn=320, vocab=1000, src=160, tgt=48, max_length=32, layers=3),
+    # timestamp mode: specials at 500-502 (EOS, start, <|notimestamps|>), 109 timestamp tokens 503..611 above them (.en layout)
+    "toy-ts": dict(_toy(vocab=612, src=96, tgt=64, max_length=48), pad_token_id=500, eos_token_id=500, bos_token_id=500,
+                   decoder_start_token_id=501, forced_decoder_ids=[[1, 502]], begin_suppress_tokens=[220, 500]),
 }
 
 

@@ -38,6 +38,8 @@ class WhisperTokenDecoder:
         if special_ids is None:  # Whisper: <|endoftext|> and every added <|...|> token are special
             special_ids = [i for t, i in list(vocab.items()) + list(self.added.items()) if t.startswith("<|") and t.endswith("|>")]
         self.special_ids = set(special_ids)
+        # timestamp tokens <|t|> sit above every special id (the reference's all_special_ids[-1] + 1, tokenization_whisper.py:504)
+        self.timestamp_begin = max(self.special_ids) + 1 if self.special_ids else max(self.id_to_token, default=-1) + 1
         self.byte_decoder = _byte_decoder()
         self.errors = errors
 
@@ -55,7 +57,7 @@ class WhisperTokenDecoder:
         parts, run = [], []
         for i in ids:
             i = int(i)
-            if skip_special_tokens and i in self.special_ids:
+            if (skip_special_tokens and i in self.special_ids) or i >= self.timestamp_begin:   # timestamps decode to nothing
                 continue
             tok = self.id_to_token[i]
             if tok in self.added:          # added tokens are literal text, not byte-level symbols
@@ -68,6 +70,39 @@ class WhisperTokenDecoder:
         if run:
             parts.append(self._bytes_to_text(run))
         return "".join(parts)
+
+    def decode_with_timestamps(self, ids: Sequence[int], skip_special_tokens: bool = False, time_precision: float = 0.02) -> str:
+        """Text with every timestamp token written as "<|1.08|>" (the reference's _decode_with_timestamps, tokenization_whisper.py:499-518)."""
+        outputs: List = [[]]
+        for i in ids:
+            i = int(i)
+            if i >= self.timestamp_begin:
+                outputs.append(f"<|{(i - self.timestamp_begin) * time_precision:.2f}|>")
+                outputs.append([])
+            else:
+                outputs[-1].append(i)
+        return "".join(o if isinstance(o, str) else self.decode(o, skip_special_tokens) for o in outputs)
+
+    def offsets(self, ids: Sequence[int], time_precision: float = 0.02) -> List[dict]:
+        """Segments [{"text", "timestamp": (start s, end s)}] between timestamp pairs (the reference's _compute_offsets,
+        tokenization_whisper.py:520-560): a segment runs from one timestamp to the next pair of consecutive timestamps (or to the
+        last timestamp); text keeps the special tokens."""
+        ids = [int(i) for i in ids]
+        is_ts = [i >= self.timestamp_begin for i in ids]
+        where = [k for k, t in enumerate(is_ts) if t]
+        cuts = [k + 1 for k in range(len(ids) - 1) if is_ts[k] and is_ts[k + 1]]
+        if not cuts and len(where) <= 1:
+            return []
+        if where[-1] + 1 not in cuts:
+            cuts.append(where[-1] + 1)
+        out, last = [], where[0]
+        for cur in cuts:
+            piece = ids[last:cur]
+            if len(piece) > 1:
+                out.append({"text": self.decode(piece, skip_special_tokens=False),
+                            "timestamp": ((piece[0] - self.timestamp_begin) * time_precision, (piece[-1] - self.timestamp_begin) * time_precision)})
+            last = cur
+        return out
 
     def batch_decode(self, batch: Iterable[Sequence[int]], skip_special_tokens: bool = True) -> List[str]:
         return [self.decode(ids, skip_special_tokens) for ids in batch]
