@@ -51,7 +51,16 @@ def parse_arguments():
     parser.add_argument("--dump_ids", type=str, default=None, help="rank 0 writes the fast-path token ids as JSON (tests)")
     parser.add_argument("--return_timestamps", action="store_true", help="Whisper's timestamp mode: <|t|> tokens (t x 0.02 s) between "
                         "segments; printed as [start --> end] text segments with a tokenizer, as ids with <|t|> marks otherwise")
+    parser.add_argument("--num_beams", type=int, default=1, help="fast path: beam search on the device with this many beams (<= 8; batches are "
+                        "sized so that utterances x beams <= 16 rows); needs a batch plan and no --return_timestamps")
+    parser.add_argument("--length_penalty", type=float, default=1.0)
+    parser.add_argument("--early_stopping", action="store_true")
     args = parser.parse_args()
+    if args.num_beams < 1 or args.num_beams > 8:
+        parser.error("--num_beams must be in [1, 8]")
+    if args.num_beams > 1 and (args.batching == "continuous" or args.return_timestamps or args.session or args.compare):
+        parser.error("--num_beams needs the fast path with a batch plan (--batching sorted | dataset): no --return_timestamps, --session or "
+                     "--compare (the Session path decodes greedily)")
     if args.return_timestamps and args.batching == "continuous":
         parser.error("--return_timestamps needs a batch plan (--batching sorted | dataset): the continuous mode predicts no timestamps")
     return args
@@ -163,14 +172,15 @@ if __name__ == "__main__":
         pipe = tensorrt_llm.WhisperPipeline(open(os.path.join(args.engine_dir, "WhisperEncoder.engine"), "rb").read(),
                                             open(os.path.join(args.engine_dir, "WhisperDecoder.engine"), "rb").read(), config, workers=max(1, args.workers))
         begin, end = tensorrt_llm.sharding.utterance_shard(len(mels), world, rank)       # this rank's contiguous shard
+        per_batch = 8 if args.num_beams <= 1 else max(1, min(8, 16 // args.num_beams))   # rows = utterances x beams <= 16
         if args.batching == "continuous":
             groups = None
         elif args.batching == "sorted":
             lengths = [tensorrt_llm.audio.valid_frames(m)[0] for m in mels]
-            groups = tensorrt_llm.sharding.length_sorted_batches(lengths, 8, world, rank)
+            groups = tensorrt_llm.sharding.length_sorted_batches(lengths, per_batch, world, rank)
         else:
             begin, end = tensorrt_llm.sharding.utterance_shard(len(mels), world, rank)   # this rank's contiguous shard
-            groups = [list(range(b0, b1)) for b0, b1 in tensorrt_llm.sharding.batches(begin, end, 8)]
+            groups = [list(range(b0, b1)) for b0, b1 in tensorrt_llm.sharding.batches(begin, end, per_batch)]
         for _ in range(2):  # the first pass is the warm-up, as in run.py:260
             if dist is not None:
                 dist.barrier()
@@ -182,6 +192,8 @@ if __name__ == "__main__":
                 indexed = list(zip(range(begin, end), [r.tolist() for r in rows]))
             else:
                 kw = [{"return_timestamps": True}] * len(groups) if args.return_timestamps else None
+                if args.num_beams > 1:
+                    kw = [{"num_beams": args.num_beams, "length_penalty": args.length_penalty, "early_stopping": args.early_stopping}] * len(groups)
                 for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):
                     indexed += list(zip(g, ids.cpu().tolist()))
             torch.cuda.synchronize()

@@ -189,6 +189,30 @@ typedef struct {
 } wt_timestamp_params;
 int wt_decoder_set_timestamp_rules(wt_engine* dec, const wt_timestamp_params* t);
 
+/* (9c) beam search for the batch decode (wt_decoder_begin / _steps / _run / _greedy), on the device: the semantics of transformers'
+ * beam_search (generation/utils.py) with BeamSearchScorer / BeamHypotheses (generation/beam_search.py), one beam group and one returned
+ * hypothesis per utterance.  Per step: log_softmax over the whole vocabulary first, then Suppress -> SuppressAtBegin -> Force on the
+ * log-probabilities, plus the running beam score (0 for beam 0, -1e9 for the others at the start); per utterance the 2 * num_beams best
+ * of the num_beams * V candidates in order (lowest flat index first among equals); an EOS candidate of rank < num_beams becomes a
+ * finished hypothesis (score = sum of log-probabilities / length ** length_penalty, the length without the EOS), the first num_beams
+ * others are the next beams; an utterance is done when its store is full and (early_stopping, or its worst kept score >= best candidate
+ * score / (cur_len + 1) ** length_penalty).  A NaN logit ranks first and is left out of its row's log-sum-exp; a row without any finite
+ * logit has a NaN log-sum-exp and only NaN / -inf candidates.  Among hypotheses of exactly equal score the returned one is unspecified
+ * (the engine takes the highest store slot, the reference the last of a stable sort).
+ * The setting applies from the next wt_decoder_begin on this handle; b == NULL or num_beams <= 1 turns it off.  With it on,
+ * wt_decoder_begin(batch = utterances) decodes batch * num_beams rows: WT_E_UNSUPPORTED when that exceeds 16, when num_beams > 8, for
+ * early_stopping outside {0, 1}, together with timestamp mode, logits_trace or force_eos_step(s), and from wt_decoder_stream_begin.
+ * wt_decoder_poll / _run report the beam stop test (every utterance done, or max_length); wt_decoder_read_ids returns the best
+ * hypothesis per utterance [batch][max_length] (EOS behind it when it fits, then pad_token_id), wt_decoder_read_beam_scores its score
+ * (device float [batch]; both are stream-ordered and may be called at any point of the decode). */
+typedef struct {
+    int32_t num_beams;
+    float length_penalty;
+    int32_t early_stopping;    /* 0: the heuristic of early_stopping=False, 1: stop at num_beams finished hypotheses */
+} wt_beam_params;
+int wt_decoder_set_beam_search(wt_engine* dec, const wt_beam_params* b);
+int wt_decoder_read_beam_scores(wt_engine* dec, float* scores_out, void* stream);
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

@@ -121,6 +121,34 @@ size_t wt_dbg_timestamp_select_scratch_bytes(int B, int V, int max_length);
 int wt_dbg_timestamp_select(const float* logits, int B, int V, int32_t* ids, int max_length, const int32_t* cur_len,
                             const wt_timestamp_params* t, int eos, int32_t* tok_out, float* stats_out, void* scratch, void* stream);
 
+/* beam search: the engine's two launches (beam_select_kernel + beam_finish_kernel) and finalize on crafted rows.  logits f32
+ * [U * nb][V], beam_scores f32 [U * nb], mask bytes [V] or NULL (bit 0: suppressed, bit 1: suppressed when cur_len == begin_index), ids
+ * int32 [U * nb][max_length] (the rows' history, cur_len ids each, 1 <= cur_len < max_length), forced_token < 0: none.  Outputs (device):
+ * cand_out int32 [U][16][3]: the sorted 2 * nb candidates (token, source beam, score bits), token -1 = none; next_out int32 [U * nb][4]:
+ * (token, source beam, score bits, utterance done) of every row; fin_ids int32 [U][max_length] / fin_scores f32 [U]: finalize after the
+ * step.  scratch: wt_dbg_beam_select_scratch_bytes(U, nb, V, max_length) bytes.  Synchronises `stream`. */
+size_t wt_dbg_beam_select_scratch_bytes(int U, int nb, int V, int max_length);
+int wt_dbg_beam_select(const float* logits, const float* beam_scores, const unsigned char* mask, int U, int nb, int V, const int32_t* ids,
+                       int max_length, int cur_len, int begin_index, int forced_token, int eos, int pad, const wt_beam_params* b,
+                       int32_t* cand_out, int32_t* next_out, int32_t* fin_ids, float* fin_scores, void* scratch, void* stream);
+/* self attention through an ancestry table (dec_attn_kernel's beam instantiation): key s of row b is read from cache row anc[b * s_cap + s]
+ * (device int32 [B][s_cap], entries in [0, B)); caches f32 or half (kv_half) [B][H][s_cap][64], unsplit */
+int wt_dbg_decode_attention_beam(const float* q, const void* kcache, const void* vcache, const int32_t* anc, float* out, int B, int H, int s_cap,
+                                 int len, int kv_half, void* stream);
+/* cross attention with rows mapped to shared cache rows (the slot_row form the beam step uses): row b reads cache row slot_row[b] (device
+ * int32 [B]) of caches [rows][H][s_cap][64], f32 or half; part / cnt as wt_dbg_decode_attention */
+int wt_dbg_decode_attention_rows(const float* q, const void* kcache, const void* vcache, const int32_t* slot_row, float* part, int* cnt, float* out,
+                                 int B, int H, int s_cap, int len, int n_split, int kv_half, void* stream);
+/* the grouped cross-attention form: caches [B / group][H][s_cap][64], cache row u shared by query rows u * group .. + group - 1, one
+ * block per (split, head, u) carrying all of them; group 2 or 4 */
+int wt_dbg_decode_attention_grouped(const float* q, const void* kcache, const void* vcache, float* part, int* cnt, float* out, int B, int H,
+                                    int s_cap, int len, int n_split, int group, int kv_half, void* stream);
+/* a beam decode in flight: the plain logits of the last executed step, device f32 [rows][V] */
+int wt_dbg_beam_logits(wt_engine* dec, float* logits_out, void* stream);
+/* a beam decode in flight: per executed step and row (token, source beam within the utterance, score bits, utterance done), device int32
+ * [steps][rows][4] */
+int wt_dbg_beam_trace(wt_engine* dec, int32_t* trace_out, int steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ ABI_VERSION = 3
 EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
-    "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
     "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_last_error", "wt_abi_version",
 ]
@@ -25,7 +25,9 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_decode_attention_folded", "wt_dbg_skinny_pair", "wt_dbg_attention_then_projection", "wt_dbg_self_attention_then_pair",
                  "wt_dbg_skinny_f16", "wt_dbg_decode_attention_f16", "wt_dbg_attention_then_projection_f16", "wt_dbg_skinny_pair_f16", "wt_dbg_gemm_f16_kv",
                  "wt_dbg_gemm_x3_tile", "wt_dbg_layernorm_split", "wt_dbg_encoder_convs_scratch_bytes", "wt_dbg_encoder_convs", "wt_dbg_cross_kv",
-                 "wt_dbg_timestamp_select_scratch_bytes", "wt_dbg_timestamp_select"]
+                 "wt_dbg_timestamp_select_scratch_bytes", "wt_dbg_timestamp_select",
+                 "wt_dbg_beam_select_scratch_bytes", "wt_dbg_beam_select", "wt_dbg_decode_attention_beam", "wt_dbg_decode_attention_rows", "wt_dbg_beam_trace",
+                 "wt_dbg_decode_attention_grouped", "wt_dbg_beam_logits"]
 
 
 class TensorDesc(Structure):
@@ -52,6 +54,10 @@ class GreedyParams(Structure):
 
 class TimestampParams(Structure):
     _fields_ = [(n, c_int32) for n in ("enabled", "no_timestamps_token_id", "timestamp_begin", "begin_index", "max_initial_timestamp_index")]
+
+
+class BeamParams(Structure):
+    _fields_ = [("num_beams", c_int32), ("length_penalty", c_float), ("early_stopping", c_int32)]
 
 
 class KernelTimer(Structure):
@@ -100,6 +106,8 @@ def load():
     lib.wt_decoder_read_ids.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.wt_decoder_greedy.argtypes = [c_void_p, c_void_p, c_int, POINTER(GreedyParams), c_void_p, POINTER(c_int), c_void_p]
     lib.wt_decoder_set_timestamp_rules.argtypes = [c_void_p, POINTER(TimestampParams)]
+    lib.wt_decoder_set_beam_search.argtypes = [c_void_p, POINTER(BeamParams)]
+    lib.wt_decoder_read_beam_scores.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -144,6 +152,14 @@ def load():
     lib.wt_dbg_timestamp_select_scratch_bytes.argtypes = [I, I, I]
     lib.wt_dbg_timestamp_select_scratch_bytes.restype = c_size_t
     lib.wt_dbg_timestamp_select.argtypes = [P, I, I, P, I, POINTER(c_int32), POINTER(TimestampParams), I, P, P, P, P]
+    lib.wt_dbg_beam_select_scratch_bytes.argtypes = [I, I, I, I]
+    lib.wt_dbg_beam_select_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_beam_select.argtypes = [P, P, P, I, I, I, P, I, I, I, I, I, I, POINTER(BeamParams), P, P, P, P, P, P]
+    lib.wt_dbg_decode_attention_beam.argtypes = [P, P, P, P, P, I, I, I, I, I, P]
+    lib.wt_dbg_decode_attention_rows.argtypes = [P, P, P, P, P, P, P, I, I, I, I, I, I, P]
+    lib.wt_dbg_beam_trace.argtypes = [c_void_p, P, I, P]
+    lib.wt_dbg_decode_attention_grouped.argtypes = [P, P, P, P, P, P, I, I, I, I, I, I, I, P]
+    lib.wt_dbg_beam_logits.argtypes = [c_void_p, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

@@ -4,6 +4,8 @@
 
 #include <string.h>
 
+#include <vector>
+
 using namespace wt;
 
 static int rc_of(hipError_t e) { return e == hipSuccess ? 0 : -5; }
@@ -337,4 +339,99 @@ extern "C" int wt_dbg_timestamp_select(const float* logits, int B, int V, int32_
     p.ts_on = 1; p.no_ts = t->no_timestamps_token_id; p.tb = t->timestamp_begin; p.ts_begin_index = t->begin_index;
     p.max_init = t->max_initial_timestamp_index; p.ts_part = (TsPart*)(base + l.part); p.ts_tok = tok_out; p.ts_stats = stats_out;
     return rc_of(launch_greedy_select(p, s));
+}
+
+// ---- beam search: the engine's launches (launch_greedy_select with beam_on, launch_beam_finalize) over crafted logits and histories ----
+struct BeamScratch { size_t st, unf, mask, forced, part, sc, ids0, ids2, anc, urow, hn, hd, hw, hs, hl, hi, total; };
+static BeamScratch beam_scratch_layout(int V, int max_length) {
+    BeamScratch l;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    const size_t R = MAX_ROWS;
+    l.st = take(sizeof(DecState)); l.unf = take(R * 4); l.mask = take((size_t)V); l.forced = take((size_t)(max_length + 1) * 4);
+    l.part = take(R * SELECT_CHUNKS * sizeof(BeamPart)); l.sc = take(R * 4); l.ids0 = take(R * max_length * 4); l.ids2 = take(R * max_length * 4);
+    l.anc = take(2 * R * max_length * 4); l.urow = take(R * 4); l.hn = take(R * 4); l.hd = take(R * 4); l.hw = take(R * 8); l.hs = take(R * 8);
+    l.hl = take(R * 4); l.hi = take(R * max_length * 4);
+    l.total = off;
+    return l;
+}
+extern "C" size_t wt_dbg_beam_select_scratch_bytes(int U, int nb, int V, int max_length) {
+    if (U < 1 || nb < 2 || nb > MAX_BEAMS || U * nb > MAX_ROWS || V < 1 || max_length < 2) return 0;
+    return beam_scratch_layout(V, max_length).total;
+}
+extern "C" int wt_dbg_beam_select(const float* logits, const float* beam_scores, const unsigned char* mask, int U, int nb, int V, const int32_t* ids,
+                                  int max_length, int cur_len, int begin_index, int forced_token, int eos, int pad, const wt_beam_params* b,
+                                  int32_t* cand_out, int32_t* next_out, int32_t* fin_ids, float* fin_scores, void* scratch, void* stream) {
+    if (!logits || !beam_scores || !ids || !b || !cand_out || !next_out || !fin_ids || !fin_scores || !scratch) return -22;
+    if (U < 1 || nb < 2 || nb > MAX_BEAMS || U * nb > MAX_ROWS || V < 1 || max_length < 2 || cur_len < 1 || cur_len >= max_length) return -22;
+    if (eos < 0 || eos >= V || pad < 0 || pad >= V || forced_token >= V || forced_token == eos || b->num_beams != nb) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    const int R = U * nb;
+    const BeamScratch l = beam_scratch_layout(V, max_length);
+    char* base = (char*)scratch;
+    DecState h;
+    memset(&h, 0, sizeof h);
+    for (int r = 0; r < MAX_ROWS; ++r) {
+        h.cur_len[r] = cur_len;
+        h.pos[r] = cur_len - 1;
+        h.self_len[r] = cur_len - 1;
+    }
+    int unf[MAX_ROWS];
+    for (int r = 0; r < MAX_ROWS; ++r) unf[r] = 1;
+    std::vector<int> forced(max_length + 1, -1);
+    forced[cur_len] = forced_token < 0 ? -1 : forced_token;
+    int rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.st, &h, sizeof h, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.unf, unf, sizeof unf, hipMemcpyHostToDevice, s)))) return rc;
+    if (mask) rc = rc_of(hipMemcpyAsync(base + l.mask, mask, (size_t)V, hipMemcpyDeviceToDevice, s));
+    else rc = rc_of(hipMemsetAsync(base + l.mask, 0, (size_t)V, s));
+    if (rc) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.forced, forced.data(), forced.size() * 4, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemsetAsync(base + l.anc, 0, 2 * (size_t)MAX_ROWS * max_length * 4, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.ids0, ids, (size_t)R * max_length * 4, hipMemcpyDeviceToDevice, s)))) return rc;
+    if ((rc = rc_of(hipStreamSynchronize(s)))) return rc;   // pageable sources
+    SelectParams p;
+    memset(&p, 0, sizeof p);
+    p.logits = logits; p.mask = (const uint8_t*)(base + l.mask); p.forced = (const int*)(base + l.forced); p.ids = (int*)(base + l.ids0);
+    p.unfinished = (int*)(base + l.unf); p.st = (DecState*)(base + l.st);
+    p.n_parts = SELECT_CHUNKS; p.B = R; p.V = V; p.max_length = max_length; p.begin_index = begin_index; p.eos = eos; p.pad = pad; p.force_eos_step = -1;
+    p.beam_on = 1;
+    BeamParams& bp = p.beam;
+    bp.nb = nb; bp.U = U; bp.length_penalty = b->length_penalty; bp.early_stopping = b->early_stopping;
+    bp.part = (BeamPart*)(base + l.part); bp.scores = (float*)(base + l.sc); bp.ids2 = (int*)(base + l.ids2); bp.anc = (int*)(base + l.anc); bp.anc_ld = max_length;
+    bp.urow = (int*)(base + l.urow); bp.hyp_n = (int*)(base + l.hn); bp.hyp_done = (int*)(base + l.hd); bp.hyp_worst = (double*)(base + l.hw);
+    bp.hyp_score = (double*)(base + l.hs); bp.hyp_len = (int*)(base + l.hl); bp.hyp_ids = (int*)(base + l.hi); bp.hyp_ld = max_length;
+    bp.out_ids = fin_ids; bp.out_scores = fin_scores; bp.trace = next_out; bp.dbg_cand = cand_out;
+    if ((rc = rc_of(launch_beam_init(p, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(bp.scores, beam_scores, (size_t)R * 4, hipMemcpyDeviceToDevice, s)))) return rc;
+    if ((rc = rc_of(launch_greedy_select(p, s)))) return rc;
+    if ((rc = rc_of(launch_beam_finalize(p, s)))) return rc;
+    return rc_of(hipStreamSynchronize(s));
+}
+extern "C" int wt_dbg_decode_attention_beam(const float* q, const void* kcache, const void* vcache, const int32_t* anc, float* out, int B, int H, int s_cap,
+                                            int len, int kv_half, void* stream) {
+    if (!q || !kcache || !vcache || !anc || !out || B < 1 || B > MAX_ROWS || len < 1 || len > s_cap) return -22;
+    DecAttnParams a;
+    memset(&a, 0, sizeof a);
+    a.q = q; a.kcache = (const float*)kcache; a.vcache = (const float*)vcache; a.out = out; a.B = B; a.H = H; a.s_cap = s_cap; a.n_split = 1;
+    a.fixed_len = len; a.nt = 1; a.kv_half = kv_half ? 1 : 0; a.anc = anc; a.anc_ld = s_cap;
+    return rc_of(launch_dec_attn(a, (hipStream_t)stream));
+}
+extern "C" int wt_dbg_decode_attention_rows(const float* q, const void* kcache, const void* vcache, const int32_t* slot_row, float* part, int* cnt, float* out,
+                                            int B, int H, int s_cap, int len, int n_split, int kv_half, void* stream) {
+    if (!q || !kcache || !vcache || !slot_row || !out || B < 1 || B > MAX_ROWS || len < 1 || len > s_cap || n_split < 1 || n_split > 16) return -22;
+    DecAttnParams a;
+    memset(&a, 0, sizeof a);
+    a.q = q; a.kcache = (const float*)kcache; a.vcache = (const float*)vcache; a.part = part; a.cnt = cnt; a.out = out; a.B = B; a.H = H; a.s_cap = s_cap;
+    a.n_split = n_split; a.fixed_len = len; a.nt = 1; a.kv_half = kv_half ? 1 : 0; a.slot_row = slot_row;
+    return rc_of(launch_dec_attn(a, (hipStream_t)stream));
+}
+extern "C" int wt_dbg_decode_attention_grouped(const float* q, const void* kcache, const void* vcache, float* part, int* cnt, float* out, int B, int H,
+                                               int s_cap, int len, int n_split, int group, int kv_half, void* stream) {
+    if (!q || !kcache || !vcache || !out || B < 1 || B > MAX_ROWS || len < 1 || len > s_cap || n_split < 1 || n_split > 16) return -22;
+    DecAttnParams a;
+    memset(&a, 0, sizeof a);
+    a.q = q; a.kcache = (const float*)kcache; a.vcache = (const float*)vcache; a.part = part; a.cnt = cnt; a.out = out; a.B = B; a.H = H; a.s_cap = s_cap;
+    a.n_split = n_split; a.fixed_len = len; a.nt = 1; a.kv_half = kv_half ? 1 : 0; a.group = group;
+    return rc_of(launch_dec_attn(a, (hipStream_t)stream));
 }

@@ -146,6 +146,12 @@ struct wt_engine {
     // decode in flight (enabled == 0: off)
     wt_timestamp_params ts_req = {0, 0, 0, 0, 0}, ts_cur = {0, 0, 0, 0, 0};
     TsPart* ts_part = nullptr;    // scratch [dec_cap][SELECT_CHUNKS] of ts_select_kernel
+    // beam search: the setting wt_decoder_set_beam_search asked for (applied by the next wt_decoder_begin) and that of the decode in
+    // flight (num_beams <= 1: off).  In a beam decode B = beam_U * num_beams rows.
+    wt_beam_params beam_req = {1, 1.f, 0}, beam_cur = {1, 1.f, 0};
+    int beam_U = 0;
+    int beam_group = 0;           // > 1: the cross-attention of the beam decode in flight runs the grouped form (num_beams 2 or 4)
+    BeamParams beam_dev = {};     // device buffers of the beam state (dec_reserve; nb / U / penalty filled per decode)
     hipStream_t own_stream = nullptr;
     // step graphs: [0] every row attends (the only one a decode without early finishers ever replays), [1] finished rows stream no K/V,
     // [2] / [3] the same two for the continuous mode (per-slot cross-cache rows, stream_finish_kernel)
@@ -662,6 +668,11 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     const size_t o_st = take(sizeof(DecState)), o_ids = take((size_t)B * cap_len * 4), o_unf = take((size_t)B * 4);
     const size_t o_forced = take((size_t)(cap_len + 1) * 4), o_mask = take((size_t)e->V), o_frows = take(16 * 4);
     const size_t o_tsp = take((size_t)B * SELECT_CHUNKS * sizeof(TsPart));
+    // beam search state (BeamParams): sized for MAX_ROWS rows whatever B, it is small
+    const size_t o_bpart = take((size_t)MAX_ROWS * SELECT_CHUNKS * sizeof(BeamPart)), o_bsc = take(MAX_ROWS * 4), o_bids2 = take((size_t)MAX_ROWS * cap_len * 4);
+    const size_t o_banc = take((size_t)2 * MAX_ROWS * cap_len * 4), o_burow = take(MAX_ROWS * 4), o_bhn = take(MAX_ROWS * 4), o_bhd = take(MAX_ROWS * 4);
+    const size_t o_bhw = take(MAX_ROWS * 8), o_bhs = take(MAX_ROWS * 8), o_bhl = take(MAX_ROWS * 4), o_bhi = take((size_t)MAX_ROWS * cap_len * 4);
+    const size_t o_bout = take((size_t)MAX_ROWS * cap_len * 4), o_bos = take(MAX_ROWS * 4), o_btr = take((size_t)cap_len * MAX_ROWS * 4 * 4);
     hipError_t he = hipMalloc((void**)&e->dec_ws, off);
     if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for decoder workspace (batch %d) failed: %s", off, B, hipGetErrorString(he));
     char* b = e->dec_ws;
@@ -669,6 +680,14 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     e->dh = (float*)(b + o_h); e->dh2 = (float*)(b + o_h2); e->dq = (float*)(b + o_q); e->datt = (float*)(b + o_att); e->att_cnt = (int*)(b + o_cnt); e->sel_val = (float*)(b + o_selv); e->sel_idx = (int*)(b + o_seli); e->dffn = (float*)(b + o_f); e->part = (float*)(b + o_part);
     e->logits = (float*)(b + o_lg); e->st = (DecState*)(b + o_st); e->ids = (int*)(b + o_ids); e->unfinished = (int*)(b + o_unf);
     e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows); e->ts_part = (TsPart*)(b + o_tsp);
+    {
+        BeamParams& bp = e->beam_dev;
+        memset(&bp, 0, sizeof bp);
+        bp.part = (BeamPart*)(b + o_bpart); bp.scores = (float*)(b + o_bsc); bp.ids2 = (int*)(b + o_bids2); bp.anc = (int*)(b + o_banc); bp.anc_ld = cap_len;
+        bp.urow = (int*)(b + o_burow); bp.hyp_n = (int*)(b + o_bhn); bp.hyp_done = (int*)(b + o_bhd); bp.hyp_worst = (double*)(b + o_bhw);
+        bp.hyp_score = (double*)(b + o_bhs); bp.hyp_len = (int*)(b + o_bhl); bp.hyp_ids = (int*)(b + o_bhi); bp.hyp_ld = cap_len;
+        bp.out_ids = (int*)(b + o_bout); bp.out_scores = (float*)(b + o_bos); bp.trace = (int*)(b + o_btr);
+    }
     e->h_force_rows.clear();
     e->enc_h = e->w_half ? (void*)(b + o_ench) : nullptr;
     e->enc3 = e->use_x3 ? (void*)(b + o_enc3) : nullptr;
@@ -707,6 +726,9 @@ struct StepIO {
     float *cross_k, *cross_v;              // layer stride = cross_rows*H*S*64 elements
     int cross_rows;                        // cache rows per layer (the engine's resident pool; 1 on the Session path)
     const int* slot_row;                   // continuous mode: slot b attends over cache row slot_row[b] (DecAttnParams.slot_row)
+    int group = 0;                         // beam search: grouped cross attention (DecAttnParams.group) instead of slot_row
+    const int* anc = nullptr;              // beam search: ancestry table of the self-attention (DecAttnParams.anc), row stride anc_ld
+    int anc_ld = 0;
     int kv_esz;                            // bytes per cache element: 4 (fp32; always on the Session path), 2 (resident caches of an fp16 engine)
     float* logits;                         // [B][V]
     int B, nsplit_self, nsplit_cross;
@@ -746,6 +768,7 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
     case LP_SELF_ATTN:
         a.q = e->dq; a.kcache = sk; a.vcache = sv; a.part = e->part; a.cnt = e->att_cnt; a.out = e->datt; a.st = e->st; a.B = B; a.H = H; a.s_cap = io.self_cap;
         a.n_split = io.nsplit_self; a.fixed_len = 0; a.nt = e->nt_loads; a.kv_half = kvh; a.alive = io.alive;
+        a.anc = io.anc; a.anc_ld = io.anc_ld;
         a.defer_merge = defer && io.nsplit_self == 2;   // both halves of the pair launch below merge the two partials while staging
         LAUNCH(launch_dec_attn(a, s));
         break;
@@ -767,6 +790,7 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
         a.q = e->dq; a.kcache = ck; a.vcache = cv; a.part = e->part; a.cnt = e->att_cnt; a.out = e->datt; a.st = e->st; a.B = B; a.H = H; a.s_cap = e->S;
         a.n_split = io.nsplit_cross; a.fixed_len = e->S; a.nt = e->nt_loads; a.ln_h = h1; a.ln_r = l.fold_r; a.ln_t = l.fold_t; a.kv_half = kvh;
         a.alive = io.alive; a.slot_row = io.slot_row;
+        if (io.group > 1) { a.group = io.group; a.slot_row = nullptr; }
         a.defer_merge = defer && io.nsplit_cross == 2;  // the out-projection below merges the two split partials while staging them
                                                         // (more splits, i.e. batch < 8: the attention kernel merges its own, by ticket)
         hipEvent_t ta, tb;
@@ -877,7 +901,8 @@ static int cross_kv_project(wt_engine* e, const float* enc_hidden, int B, int ro
 
 // Everything wt_decoder_begin and wt_decoder_stream_begin share: argument checks, workspace, token-rule tables, cache policy and key
 // splits of the step graph.  `B` = rows of the batch / decode slots of the stream; `pool_rows` = cross-cache rows (0: B).
-static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool_rows, bool stream_mode, hipStream_t s, const char* who) {
+static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool_rows, bool stream_mode, hipStream_t s, const char* who,
+                        const wt_beam_params beam = wt_beam_params{1, 1.f, 0}) {
     if (B > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "%s: batch %d > %d per call; shard the batch", who, B, MAX_ROWS);
     if (p->max_length < 2 || p->max_length > e->T) return fail(WT_E_INVALID, "max_length %d outside [2, max_target_positions=%d]", p->max_length, e->T);
     auto tok_ok = [&](int t) { return t >= 0 && t < e->V; };
@@ -905,6 +930,8 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
         if (ts.enabled && (tok == ts.no_timestamps_token_id || idx >= ts.begin_index - 1))   // Force and Timestamp must not fight
             return fail(WT_E_INVALID, "timestamp mode: forced token %d at %d (no <|notimestamps|>, no forced position >= begin_index - 1 = %d)",
                         tok, idx, ts.begin_index - 1);
+        if (beam.num_beams > 1 && tok == p->eos_token_id)
+            return fail(WT_E_INVALID, "beam search: forced token %d is the EOS token (no beam could continue)", tok);
         if (idx >= 0 && idx <= e->dec_maxlen_cap) forced[idx] = tok;
     }
     if (!e->tables_valid || mask != e->h_mask || forced != e->h_forced) {
@@ -931,9 +958,10 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
     const bool same = e->begun && e->B == B && e->max_length == p->max_length && e->trace == p->logits_trace &&
                       e->begin_index == p->begin_index && e->eos == p->eos_token_id && e->pad == p->pad_token_id &&
                       e->force_eos_step == p->force_eos_step && e->start_token == p->decoder_start_token_id &&
-                      memcmp(&e->ts_cur, &ts, sizeof ts) == 0;
+                      memcmp(&e->ts_cur, &ts, sizeof ts) == 0 && memcmp(&e->beam_cur, &beam, sizeof beam) == 0;
     if (!same) e->graph_valid = false;
     e->ts_cur = ts;
+    e->beam_cur = beam;
     e->B = B; e->max_length = p->max_length; e->begin_index = p->begin_index; e->eos = p->eos_token_id;
     e->pad = p->pad_token_id; e->force_eos_step = p->force_eos_step; e->trace = p->logits_trace; e->start_token = p->decoder_start_token_id;
     // measured (tools/microbench.py, medium.en B=8): self attention is fastest unsplit at every length <= 448;
@@ -958,7 +986,23 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
         if (ns != e->nsplit_self) e->graph_valid = false;
         e->nsplit_self = ns;
     }
-    e->nsplit_cross = tuning_env("WT_NSPLIT_CROSS") ? atoi(tuning_env("WT_NSPLIT_CROSS")) : pick_splits(B, e->H, e->S);
+    {   // beam search: the cross-attention form.  The shared cache rows are read once per beam through slot_row (B blocks per head).  The
+        // grouped form (one block per (utterance, head, split) carrying all beams; num_beams 2 and 4) measured SLOWER at medium.en 4 x 4:
+        // 28.5 against 17.6 us per launch (per-row reading of 16 rows: 32.2), profiles/beam_cost.json -- it is kept as an A/B only:
+        // WT_BEAM_CROSS=grouped (read per decode, so one handle can time both: tools/beam_cost.py).
+        const char* form = tuning_env("WT_BEAM_CROSS");
+        int group = 0;
+        if (form && !strcmp(form, "grouped") && (beam.num_beams == 2 || beam.num_beams == 4) && !stream_mode) group = beam.num_beams;
+        if (group != e->beam_group) e->graph_valid = false;
+        e->beam_group = group;
+        if (beam.num_beams > 1 && e->nsplit_self != 1) { e->nsplit_self = 1; e->graph_valid = false; }   // the ancestry form is unsplit
+    }
+    {
+        const int rows = e->beam_group > 1 ? B / e->beam_group : B;   // blocks per head and split
+        const int ns = tuning_env("WT_NSPLIT_CROSS") ? atoi(tuning_env("WT_NSPLIT_CROSS")) : pick_splits(rows, e->H, e->S);
+        if (ns != e->nsplit_cross) e->graph_valid = false;
+        e->nsplit_cross = ns;
+    }
     e->epoch = e->epoch % 0xffff + 1;   // 1..65535: never the value of a freshly zeroed mailbox
     e->issued = 0;
     e->stream_mode = stream_mode;
@@ -981,21 +1025,57 @@ extern "C" int wt_decoder_set_timestamp_rules(wt_engine* e, const wt_timestamp_p
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_beam_search(wt_engine* e, const wt_beam_params* b) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_beam_search: not a decoder engine");
+    if (!b || b->num_beams <= 1) {
+        e->beam_req = wt_beam_params{1, 1.f, 0};
+        return WT_OK;
+    }
+    if (b->num_beams > MAX_BEAMS) return fail(WT_E_UNSUPPORTED, "wt_decoder_set_beam_search: num_beams %d > %d", b->num_beams, MAX_BEAMS);
+    if (b->early_stopping != 0 && b->early_stopping != 1)
+        return fail(WT_E_UNSUPPORTED, "wt_decoder_set_beam_search: early_stopping %d (0 or 1; \"never\" is not supported)", b->early_stopping);
+    if (!(b->length_penalty == b->length_penalty) || fabsf(b->length_penalty) > 1e3f)
+        return fail(WT_E_INVALID, "wt_decoder_set_beam_search: length_penalty %g", (double)b->length_penalty);
+    e->beam_req = *b;
+    return WT_OK;
+}
+
+static void fill_select_params(wt_engine* e, SelectParams& sp);
+
 extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, const wt_greedy_params* p, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_begin: not a decoder engine");
     if (!enc_hidden || !p || B < 1) return fail(WT_E_INVALID, "wt_decoder_begin: bad arguments");
+    // beam search: `B` utterances decode as B * num_beams rows, [utterance][beam]
+    const wt_beam_params beam = e->beam_req;
+    const int nb = beam.num_beams > 1 ? beam.num_beams : 1, U = B;
+    if (nb > 1) {
+        if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and timestamp mode cannot be combined");
+        if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
+            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: logits_trace / force_eos_step(s) are not available with beam search");
+        if (U * nb > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", U, nb, MAX_ROWS);
+        B = U * nb;
+    }
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    int rc = decode_setup(e, B, p, 0, false, s, "wt_decoder_begin");
+    int rc = decode_setup(e, B, p, 0, false, s, "wt_decoder_begin", nb > 1 ? beam : wt_beam_params{1, 1.f, 0});
     if (rc) return rc;
+    e->beam_U = U;
     LAUNCH(launch_dec_init(e->st, e->ids, e->unfinished, B, p->max_length, p->decoder_start_token_id, e->epoch, s));
+    if (nb > 1) {
+        SelectParams sp;
+        fill_select_params(e, sp);
+        LAUNCH(launch_beam_init(sp, s));
+    }
     LAUNCH(launch_dec_embed(e->ids, p->max_length, e->tok_emb, e->pos_emb, e->dh, B, e->d, e->st, s, e->w_half));  // input of step 0
-    rc = cross_kv_project(e, enc_hidden, B, e->S, 0, e->cross_k, e->cross_v, e->kv_esz, s, e->cross_rows, 0);
+    // the beams of an utterance attend over the same encoder memory: its cross K/V are projected once, into cache row u
+    rc = cross_kv_project(e, enc_hidden, U, e->S, 0, e->cross_k, e->cross_v, e->kv_esz, s, e->cross_rows, 0);
     if (rc) return rc;
     e->begun = true;
     return WT_OK;
 }
+
+static bool beam_on(const wt_engine* e) { return e->beam_cur.num_beams > 1 && !e->stream_mode; }
 
 static void fill_select_params(wt_engine* e, SelectParams& sp) {
     memset(&sp, 0, sizeof sp);
@@ -1010,6 +1090,11 @@ static void fill_select_params(wt_engine* e, SelectParams& sp) {
         sp.ts_on = 1; sp.no_ts = e->ts_cur.no_timestamps_token_id; sp.tb = e->ts_cur.timestamp_begin;
         sp.ts_begin_index = e->ts_cur.begin_index; sp.max_init = e->ts_cur.max_initial_timestamp_index; sp.ts_part = e->ts_part;
     }
+    if (beam_on(e)) {
+        sp.beam_on = 1; sp.beam = e->beam_dev;
+        sp.beam.nb = e->beam_cur.num_beams; sp.beam.U = e->beam_U; sp.beam.length_penalty = e->beam_cur.length_penalty;
+        sp.beam.early_stopping = e->beam_cur.early_stopping;
+    }
     if (e->stream_mode) {
         sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1; sp.force_eos_rows = nullptr; sp.trace = nullptr;
     }
@@ -1022,12 +1107,13 @@ static int enqueue_fast_step(wt_engine* e, hipStream_t s, int variant = 0) {
     io.ids = e->ids; io.ids_ld = e->max_length; io.self_k = e->self_k; io.self_v = e->self_v; io.self_cap = e->T;
     io.cross_k = e->cross_k; io.cross_v = e->cross_v; io.cross_rows = e->cross_rows; io.logits = e->logits; io.B = e->B; io.kv_esz = e->kv_esz;
     io.slot_row = (variant & 2) ? e->st->slot_row : nullptr;   // (address arithmetic on a device pointer: nothing is dereferenced here)
+    if (beam_on(e)) { io.slot_row = e->beam_dev.urow; io.anc = e->beam_dev.anc; io.anc_ld = e->beam_dev.anc_ld; io.group = e->beam_group; }
     io.nsplit_self = e->nsplit_self; io.nsplit_cross = e->nsplit_cross;
     io.embed = false;  // dh already holds this step's input: written by wt_decoder_begin (step 0) or by the previous greedy_finish
     static const bool fuse = tuning_env("WT_NO_FUSED_ARGMAX") == nullptr;  // A/B switch: logits to HBM + greedy_select_kernel
     SelectParams sp;
     fill_select_params(e, sp);
-    const bool fused = fuse && !sp.ts_on;   // timestamp mode: plain logits to HBM, then ts_select_kernel
+    const bool fused = fuse && !sp.ts_on && !sp.beam_on;   // timestamp mode / beam search: plain logits to HBM, then their select kernels
     int parts = 0;
     io.argmax = fused ? &sp : nullptr;
     io.argmax_parts = &parts;
@@ -1048,7 +1134,7 @@ static std::mutex g_capture_mutex;
 // no K/V (wt_decoder_run switches to it once the mailbox reports a finished row; never with a logits trace, which records every
 // row's logits at every step as the reference computes them).  The continuous mode replays variants 2 / 3.
 static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant = 0) {
-    if (e->trace) variant = 0;
+    if (e->trace || beam_on(e)) variant = 0;   // (beam search: one graph; a finished utterance's rows keep attending)
     if (e->stream_mode) variant |= 2;
     if (e->profiling || !e->use_graph) {  // eager: per-kernel event timers need real launches
         for (int i = 0; i < n_steps; ++i) {
@@ -1107,6 +1193,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     if (pool_rows <= 0) pool_rows = 4 * slots;     // slots decoding + 3 x slots prepared ahead
     if (pool_rows < slots + 1 || pool_rows > STREAM_QCAP) return fail(WT_E_INVALID, "wt_decoder_stream_begin: pool of %d rows outside [slots + 1, %d]", pool_rows, STREAM_QCAP);
     if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: timestamp mode is a batch-decode feature (wt_decoder_begin)");
+    if (e->beam_req.num_beams > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: beam search is a batch-decode feature (wt_decoder_begin)");
     if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);
@@ -1353,8 +1440,48 @@ extern "C" int wt_decoder_read_ids(wt_engine* e, int32_t* ids_out, int ld, void*
     if (!ids_out || ld < e->max_length) return fail(WT_E_INVALID, "wt_decoder_read_ids: row stride %d < max_length %d", ld, e->max_length);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
+    if (beam_on(e)) {   // the best hypothesis of every utterance: finalize runs on the stream, behind the steps
+        SelectParams sp;
+        fill_select_params(e, sp);
+        LAUNCH(launch_beam_finalize(sp, (hipStream_t)stream));
+        HIPCHK(hipMemcpy2DAsync(ids_out, (size_t)ld * 4, e->beam_dev.out_ids, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->beam_U,
+                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        return WT_OK;
+    }
     HIPCHK(hipMemcpy2DAsync(ids_out, (size_t)ld * 4, e->ids, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->B,
                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+
+extern "C" int wt_decoder_read_beam_scores(wt_engine* e, float* scores_out, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !beam_on(e)) return fail(WT_E_STATE, "wt_decoder_read_beam_scores: no beam decode in flight");
+    if (!scores_out) return fail(WT_E_INVALID, "wt_decoder_read_beam_scores: null output");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    SelectParams sp;
+    fill_select_params(e, sp);
+    LAUNCH(launch_beam_finalize(sp, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(scores_out, e->beam_dev.out_scores, (size_t)e->beam_U * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+
+// debug read-back: the plain logits [rows][V] the last executed step of a beam decode left in HBM
+extern "C" int wt_dbg_beam_logits(wt_engine* e, float* logits_out, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !beam_on(e)) return fail(WT_E_STATE, "wt_dbg_beam_logits: no beam decode in flight");
+    if (!logits_out) return fail(WT_E_INVALID, "wt_dbg_beam_logits: null output");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    HIPCHK(hipMemcpyAsync(logits_out, e->logits, (size_t)e->B * e->V * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+
+// debug read-back (whisper_trtllm_amd_debug.h): per executed step and row (token, source beam within the utterance, score bits, utterance done)
+extern "C" int wt_dbg_beam_trace(wt_engine* e, int32_t* trace_out, int steps, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !beam_on(e)) return fail(WT_E_STATE, "wt_dbg_beam_trace: no beam decode in flight");
+    if (!trace_out || steps < 1 || steps > e->max_length - 1) return fail(WT_E_INVALID, "wt_dbg_beam_trace: %d steps outside [1, max_length - 1]", steps);
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    HIPCHK(hipMemcpyAsync(trace_out, e->beam_dev.trace, (size_t)steps * e->B * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 
@@ -1498,6 +1625,7 @@ extern "C" int wt_decoder_time_kernel(wt_engine* e, const char* which, int iters
     io.cross_k = e->cross_k; io.cross_v = e->cross_v; io.cross_rows = e->cross_rows; io.logits = e->logits; io.B = e->B; io.kv_esz = e->kv_esz;
     io.nsplit_self = e->nsplit_self; io.nsplit_cross = e->nsplit_cross; io.embed = false; io.argmax = nullptr; io.argmax_parts = nullptr;
     io.alive = nullptr; io.slot_row = nullptr;
+    if (beam_on(e)) { io.slot_row = e->beam_dev.urow; io.anc = e->beam_dev.anc; io.anc_ld = e->beam_dev.anc_ld; io.group = e->beam_group; }   // as the beam step runs them
     struct ProfilingOff {   // no event records inside the capture; the caller's setting comes back on every exit path
         wt_engine* e; bool was;
         explicit ProfilingOff(wt_engine* e_) : e(e_), was(e_->profiling) { e->profiling = false; }

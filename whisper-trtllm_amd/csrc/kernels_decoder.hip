@@ -665,17 +665,25 @@ __device__ __forceinline__ float row8_allreduce_sum(float v) {   // sum over eac
 // in flight per CU (the kernel is bound by round trips x bytes in flight, not by the HBM rate: it takes 17.1 us with a layer's K/V
 // resident in the Infinity Cache and 17.8 from HBM).
 // SLOT (continuous mode, cross attention): slot b's keys / values live in cache row slot_row[b] of a pool, not in row b.
-template <int U, bool NT, bool KVH, bool PIPE = false, bool ALIVE = false, int NTHR = 256, bool SLOT = false>
+// ANC (beam search, self attention): key s of row b lives in cache row anc[b][s] -- after a beam step row b continues the history of
+// another row, and instead of regathering the caches (L x 2 x rows x H x t x 64 elements read and written per step) only the row part
+// of every key address comes from the ancestry table (one 4-byte load per key, shared by the lanes of that key); the 16-byte key
+// loads, the streams and their order are those of the plain kernel, so the result is bitwise that of a regathered cache.
+// G > 1 (beam search, cross attention, grouped form): the G beams of an utterance share its K/V, so ONE block streams cache row
+// blockIdx.z and carries the G query rows blockIdx.z * G + g against every key tile -- the keys are in registers already; it is G dot
+// products and online-softmax states per key instead of one, and the K/V stream is paid once per utterance instead of once per beam.
+template <int U, bool NT, bool KVH, bool PIPE = false, bool ALIVE = false, int NTHR = 256, bool SLOT = false, bool ANC = false, int G = 1>
 __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
     constexpr int LPK = KVH ? 8 : 16;          // lanes per key
     constexpr int DPL = HEAD_DIM / LPK;        // head dims per lane: 8 or 4 (16 bytes of K or V either way)
     constexpr int NSTR = NTHR / LPK;           // online-softmax streams per block
     constexpr int KSZ = KVH ? 2 : 4;
-    __shared__ float sm_o[NSTR][HEAD_DIM];
-    __shared__ float sm_m[NSTR], sm_l[NSTR];
+    static_assert(G == 1 || (!ALIVE && !SLOT && !ANC), "the grouped form is its own addressing");
+    __shared__ float sm_o[G][NSTR][HEAD_DIM];
+    __shared__ float sm_m[G][NSTR], sm_l[G][NSTR];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & (LPK - 1), sid = tid / LPK;
-    const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+    const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z * G;   // (G > 1: the first of the block's query rows)
     const int len = p.fixed_len > 0 ? p.fixed_len : p.st->self_len[b] + 1;
     const int chunk = (len + p.n_split - 1) / p.n_split;
     const int s_begin = split * chunk, s_end = min(len, s_begin + chunk);
@@ -688,14 +696,23 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
     const int nstr = (NTHR == 256 || nkeys >= 128) ? NSTR : NSTR / 2;
     if (NTHR != 256 && sid >= nstr) return;   // wave-uniform (LPK divides 64)
 
-    const int crow = SLOT ? max(p.slot_row[b], 0) : b;   // (an idle slot reads row 0: finite values nobody uses)
+    const int crow = G > 1 ? (int)blockIdx.z : SLOT ? max(p.slot_row[b], 0) : b;   // (an idle slot reads row 0: finite values nobody uses)
     const char* kb = reinterpret_cast<const char*>(p.kcache) + (((size_t)crow * p.H + h) * p.s_cap * HEAD_DIM + DPL * c) * KSZ;
     const char* vb = reinterpret_cast<const char*>(p.vcache) + (((size_t)crow * p.H + h) * p.s_cap * HEAD_DIM + DPL * c) * KSZ;
     typedef float f4v __attribute__((ext_vector_type(4)));   // 16 raw bytes
+    const int* anc_row = nullptr;
+    if constexpr (ANC) anc_row = p.anc + ((size_t)(p.st ? (p.st->step & 1) : 0) * MAX_ROWS + b) * p.anc_ld;
+    const size_t row_bytes = (size_t)p.H * p.s_cap * HEAD_DIM * KSZ;
+    // byte offset of key ks from kb / vb (ANC: kb / vb are row b's, the table gives the row that really holds the key)
+    auto key_off = [&](const int ks) -> long long {
+        long long off = (long long)ks * (HEAD_DIM * KSZ);
+        if constexpr (ANC) off += ((long long)anc_row[ks] - crow) * (long long)row_bytes;
+        return off;
+    };
     auto load_tile = [&](f4v (&kk)[U], f4v (&vv)[U], const int s0) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const size_t key = (size_t)min(s0 + nstr * u, s_end - 1) * (HEAD_DIM * KSZ);
+            const long long key = key_off(min(s0 + nstr * u, s_end - 1));
             if (NT) {  // K/V are read exactly once per step: non-temporal loads keep them from displacing weights in L2
                 kk[u] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(kb + key));
                 vv[u] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(vb + key));
@@ -727,7 +744,7 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
     auto load_half = [&](const int h, const int s0) {   // half-tile h = registers [h * UH, (h + 1) * UH); unconditional clamped loads
 #pragma unroll
         for (int u = 0; u < UH; ++u) {
-            const size_t key = (size_t)min(s0 + nstr * u, s_end - 1) * (HEAD_DIM * KSZ);
+            const long long key = key_off(min(s0 + nstr * u, s_end - 1));
             if (NT) {
                 kk[h * UH + u] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(kb + key));
                 vv[h * UH + u] = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(vb + key));
@@ -746,11 +763,14 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
         if (s_first < s_end) load_tile(kk, vv, s_first);
     }
 
-    float q[DPL];
+    float q[G][DPL];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
 #pragma unroll
     for (int i = 0; i < DPL; i += 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p.q + (size_t)b * d + h * HEAD_DIM + DPL * c + i);
-        q[i] = t.x; q[i + 1] = t.y; q[i + 2] = t.z; q[i + 3] = t.w;
+        const float4 t = *reinterpret_cast<const float4*>(p.q + (size_t)(b + g) * d + h * HEAD_DIM + DPL * c + i);
+        q[g][i] = t.x; q[g][i + 1] = t.y; q[g][i + 2] = t.z; q[g][i + 3] = t.w;
+    }
     }
     if (p.ln_h) {
         // folded query: finish the LayerNorm of the residual row here (every wave for itself: d <= 1024 floats, no barrier),
@@ -763,7 +783,9 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
             r[i] = r4.x; r[i + 1] = r4.y; r[i + 2] = r4.z; r[i + 3] = r4.w;
             t[i] = t4.x; t[i + 1] = t4.y; t[i + 2] = t4.z; t[i + 3] = t4.w;
         }
-        const float* hr = p.ln_h + (size_t)b * d;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+        const float* hr = p.ln_h + (size_t)(b + g) * d;
         float4 hv[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v)  // unconditional loads from clamped addresses, all four in flight before the first use
@@ -785,7 +807,8 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
             }
         const float rstd = rsqrtf(wave_allreduce_sum_d(sq) / d + 1e-5f);
 #pragma unroll
-        for (int i = 0; i < DPL; ++i) q[i] = (q[i] - mean * r[i]) * rstd + t[i];
+        for (int i = 0; i < DPL; ++i) q[g][i] = (q[g][i] - mean * r[i]) * rstd + t[i];
+        }
     }
     // A finished row pads whatever it computes (run.py:219-226 stops a batch-1 decode at its own EOS): in the step graph that
     // wt_decoder_run switches to once a row has finished, such a row leaves here and streams no K/V.  (The test costs the dominant
@@ -793,42 +816,60 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
     if constexpr (ALIVE) {   // a compile-time form: the all-rows-alive graph runs the kernel exactly as it was
         if (p.alive[b] == 0) return;   // block-uniform
     }
-    float m = -INFINITY, l = 0.f;
-    float acc[DPL];
+    float m[G], l[G];
+    float acc[G][DPL];
 #pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
+    for (int g = 0; g < G; ++g) {
+        m[g] = -INFINITY;
+        l[g] = 0.f;
+#pragma unroll
+        for (int i = 0; i < DPL; ++i) acc[g][i] = 0.f;
+    }
     auto consume = [&](const int h, const int s0) {   // online-softmax update with the UH keys of half-tile h (first key s0 < s_end)
-        float sc[UH];
-        float mx = m;
+        float sc[G][UH];
+        float mx[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) mx[g] = m[g];
 #pragma unroll
         for (int u = 0; u < UH; ++u) {
             float kf[DPL];
             widen(kk[h * UH + u], kf);
-            float dot = q[DPL - 1] * kf[DPL - 1];
 #pragma unroll
-            for (int i = DPL - 2; i >= 0; --i) dot = fmaf(q[i], kf[i], dot);
-            sc[u] = KVH ? row8_allreduce_sum(dot) : row16_allreduce_sum(dot);
-            if (s0 + nstr * u >= s_end) sc[u] = -INFINITY;
-            mx = fmaxf(mx, sc[u]);
+            for (int g = 0; g < G; ++g) {
+                float dot = q[g][DPL - 1] * kf[DPL - 1];
+#pragma unroll
+                for (int i = DPL - 2; i >= 0; --i) dot = fmaf(q[g][i], kf[i], dot);
+                sc[g][u] = KVH ? row8_allreduce_sum(dot) : row16_allreduce_sum(dot);
+                if (s0 + nstr * u >= s_end) sc[g][u] = -INFINITY;
+                mx[g] = fmaxf(mx[g], sc[g][u]);
+            }
         }
         // plain form: s0 < s_end, so u = 0 is a real key and mx is finite.  PIPE consumes branch-free (a skipped consumer would make
         // the waitcnt pass merge "loads pending" with "loads waited for" and drain vmcnt(0) in front of every request): a stream
         // past its last key has every score at -inf, keeps m, and rescales by exp(0) -- or by 0 while it has seen no key at all.
-        const float mxs = PIPE && mx == -INFINITY ? 0.f : mx;
-        const float alpha = __expf(m - mxs);
-        l *= alpha;
+        float mxs[G];
 #pragma unroll
-        for (int i = 0; i < DPL; ++i) acc[i] *= alpha;
+        for (int g = 0; g < G; ++g) {
+            mxs[g] = PIPE && mx[g] == -INFINITY ? 0.f : mx[g];
+            const float alpha = __expf(m[g] - mxs[g]);
+            l[g] *= alpha;
+#pragma unroll
+            for (int i = 0; i < DPL; ++i) acc[g][i] *= alpha;
+        }
 #pragma unroll
         for (int u = 0; u < UH; ++u) {
-            const float pr = __expf(sc[u] - mxs);
-            l += pr;
             float vf[DPL];
             widen(vv[h * UH + u], vf);
 #pragma unroll
-            for (int i = 0; i < DPL; ++i) acc[i] = fmaf(pr, vf[i], acc[i]);
+            for (int g = 0; g < G; ++g) {
+                const float pr = __expf(sc[g][u] - mxs[g]);
+                l[g] += pr;
+#pragma unroll
+                for (int i = 0; i < DPL; ++i) acc[g][i] = fmaf(pr, vf[i], acc[g][i]);
+            }
         }
-        m = mx;
+#pragma unroll
+        for (int g = 0; g < G; ++g) m[g] = mx[g];
     };
     if constexpr (PIPE) {
         const int stride = nstr * U;
@@ -860,38 +901,45 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
         }
     }
 #pragma unroll
-    for (int i = 0; i < DPL; i += 4) *reinterpret_cast<float4*>(&sm_o[sid][DPL * c + i]) = make_float4(acc[i], acc[i + 1], acc[i + 2], acc[i + 3]);
-    if (c == 0) {
-        sm_m[sid] = m;
-        sm_l[sid] = l;
+    for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int i = 0; i < DPL; i += 4)
+            *reinterpret_cast<float4*>(&sm_o[g][sid][DPL * c + i]) = make_float4(acc[g][i], acc[g][i + 1], acc[g][i + 2], acc[g][i + 3]);
+        if (c == 0) {
+            sm_m[g][sid] = m[g];
+            sm_l[g][sid] = l[g];
+        }
     }
     __syncthreads();
     if (wave != 0) return;  // wave-uniform: only wave 0 publishes / merges
+    // one query row at a time (G > 1: the block's rows b .. b + G - 1)
+    auto finish_row = [&](const int g) {
+    const int bg = b + g;
     // merge of the streams' partials by wave 0, with a COMPILE-TIME trip count in either case (a run-time bound keeps hipcc from issuing
     // the LDS reads of all partials ahead of the first exp: the loop then pays one LDS round trip per stream)
     float M, o = 0.f, L = 0.f;
     auto merge = [&](auto COUNT) {
         constexpr int n = decltype(COUNT)::value;
-        M = sm_m[0];
+        M = sm_m[g][0];
 #pragma unroll
-        for (int i = 1; i < n; ++i) M = fmaxf(M, sm_m[i]);
+        for (int i = 1; i < n; ++i) M = fmaxf(M, sm_m[g][i]);
         if (M > -INFINITY) {
 #pragma unroll
             for (int i = 0; i < n; ++i) {
-                const float w = __expf(sm_m[i] - M);  // streams with no key have m = -inf -> weight 0
-                o = fmaf(w, sm_o[i][lane], o);
-                L = fmaf(w, sm_l[i], L);
+                const float w = __expf(sm_m[g][i] - M);  // streams with no key have m = -inf -> weight 0
+                o = fmaf(w, sm_o[g][i][lane], o);
+                L = fmaf(w, sm_l[g][i], L);
             }
         }
     };
     if (NTHR == 256 || nstr == NSTR) merge(std::integral_constant<int, NSTR>{});
     else merge(std::integral_constant<int, NSTR / 2>{});
-    float* outp = p.out + (size_t)b * d + h * HEAD_DIM;
+    float* outp = p.out + (size_t)bg * d + h * HEAD_DIM;
     if (p.n_split == 1) {
         outp[lane] = o / L;
         return;
     }
-    float* pbase = p.part + ((size_t)b * p.H + h) * p.n_split * PART_STRIDE;
+    float* pbase = p.part + ((size_t)bg * p.H + h) * p.n_split * PART_STRIDE;
     float* pp = pbase + split * PART_STRIDE;
     if (p.defer_merge) {  // the consumer GEMV merges the splits while it stages its activations (kernel boundary = visibility)
         pp[lane] = o;
@@ -911,7 +959,7 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     int last = 0;
     if (lane == 0) {
-        const int ticket = __hip_atomic_fetch_add(p.cnt + b * p.H + h, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int ticket = __hip_atomic_fetch_add(p.cnt + bg * p.H + h, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         last = ticket == p.n_split - 1;
     }
     last = __shfl(last, 0);
@@ -931,7 +979,10 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
         Lg = fmaf(w, ls, Lg);
     }
     outp[lane] = og / Lg;
-    if (lane == 0) p.cnt[b * p.H + h] = 0;  // re-arm the ticket for the next launch (kernel boundary orders it)
+    if (lane == 0) p.cnt[bg * p.H + h] = 0;  // re-arm the ticket for the next launch (kernel boundary orders it)
+    };
+#pragma unroll
+    for (int g = 0; g < G; ++g) finish_row(g);
 }
 hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s) {
     // A/B override: WT_ATTN_VARIANT=0 forces default-policy loads, 1 forces non-temporal loads (2: as the engine asks).  A function-local
@@ -955,6 +1006,33 @@ hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s) {
     // (sixteen-wave blocks measured SLOWER than eight: cross-attention 19.2 -> 20.6 us, self-attention at 224 keys 5.9 -> 6.4)
     // (and four keys per stream and iteration stay best in the eight-wave form: U = 2 / 4 / 8 -> 19.9 / 19.8 / 20.1 us cross-attention,
     //  6.3 / 5.8 / 6.0 us self-attention at 224 keys)
+    if (p.group > 1) {   // beam search, cross attention, grouped form: grid z = utterances, `group` query rows per block
+        if (p.anc || p.alive || p.slot_row || p.B % p.group != 0 || (p.group != 2 && p.group != 4)) return hipErrorInvalidValue;
+        const dim3 gg(p.n_split, p.H, p.B / p.group);
+        if (!p.kv_half) {
+            if (p.group == 2 && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, false, 2>), gg, dim3(512), 0, s, p);
+            else if (p.group == 2) hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, false, 2>), gg, dim3(512), 0, s, p);
+            else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, false, 4>), gg, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, false, 4>), gg, dim3(512), 0, s, p);
+        } else {
+            if (p.group == 2 && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, false, 2>), gg, dim3(256), 0, s, p);
+            else if (p.group == 2) hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, false, 2>), gg, dim3(256), 0, s, p);
+            else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, false, 4>), gg, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, false, 4>), gg, dim3(256), 0, s, p);
+        }
+        return hipGetLastError();
+    }
+    if (p.anc) {   // beam search: the self-attention launches of the step graph, same block shapes as the plain forms below
+        if (p.n_split != 1 || p.slot_row || p.alive || p.anc_ld < p.s_cap) return hipErrorInvalidValue;
+        if (!p.kv_half) {
+            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, true>), grid, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, true>), grid, dim3(512), 0, s, p);
+        } else {
+            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, true>), grid, dim3(256), 0, s, p);
+        }
+        return hipGetLastError();
+    }
     if (p.slot_row) {   // continuous mode: the cross-attention launches of the step graph (the engine's own plans only)
         if (!p.kv_half) {
             if (p.alive && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, true, 512, true>), grid, dim3(512), 0, s, p);
@@ -1483,9 +1561,446 @@ hipError_t launch_stream_publish(const SelectParams& p, const StreamPublish& pub
     return hipGetLastError();
 }
 
+// ---- beam search (wt_decoder_set_beam_search): the reference's beam_search (transformers generation/utils.py) with BeamSearchScorer /
+// BeamHypotheses (generation/beam_search.py), one group and one returned hypothesis per utterance.  Rows are [utterance][beam].  Per
+// step: scores = log_softmax(logits) over the whole vocabulary, THEN Suppress -> SuppressAtBegin -> Force on the log-probabilities,
+// plus the row's running beam score; per utterance the 2 * nb best of the nb * V candidates, sorted, lowest flat index (beam * V + id)
+// first among equals; walking them, an EOS candidate of rank < nb becomes a finished hypothesis and the first nb others the next beams.
+//   beam_select_kernel  grid (SELECT_CHUNKS, B): per chunk the (max, sum-exp) pair over ALL ids and the 2 * nb best ids under the masks;
+//   beam_finish_kernel  one block, a wave per utterance: merge, top 2 * nb, the scorer's `process` (hypothesis store, is_done), then
+//                       the block re-parents id history and ancestry table and does greedy_finish_kernel's bookkeeping;
+//   beam_finalize_kernel grid (U): BeamSearchScorer.finalize (open beams of unfinished utterances join, best hypothesis out).
+// A NaN logit is a candidate that ranks first (as in the argmax kernels) and is left out of the log-sum-exp of its row.
+constexpr int BEAM_NONE = 0x7fffffff;
+
+__device__ __forceinline__ void beam_wave_best(float& v, int& i) {   // all-reduce of the best (v, i) over a wave
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        if (argmax_better(ov, oi, v, i)) {
+            v = ov;
+            i = oi;
+        }
+    }
+}
+__device__ __forceinline__ void beam_wave_lse(float& m, float& s) {   // all-reduce of an online (max, sum-exp) pair over a wave
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float om = __shfl_xor(m, o), os = __shfl_xor(s, o);
+        const float nm = fmaxf(m, om);
+        s = ts_rescale(s, m, nm) + ts_rescale(os, om, nm);
+        m = nm;
+    }
+}
+
+__global__ __launch_bounds__(256) void beam_select_kernel(const SelectParams p) {
+    __shared__ float s_v[4][BEAM_KMAX];
+    __shared__ int s_i[4][BEAM_KMAX];
+    __shared__ float s_m[4], s_s[4];
+    const DecState* st = p.st;
+    if (st->done) return;  // steps enqueued past the stop test are no-ops
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, chunk = blockIdx.x, b = blockIdx.y;
+    const bool at_begin = st->cur_len[b] == p.begin_index;
+    const int K = 2 * p.beam.nb;
+    const float* lg = p.logits + (size_t)b * p.V;
+    const int per = (p.V + SELECT_CHUNKS - 1) / SELECT_CHUNKS;
+    const int v0 = chunk * per, v1 = min(p.V, v0 + per);
+    // the log-softmax denominator runs over every id, masked or not (the processors act on the log-probabilities)
+    float m = -INFINITY, z = 0.f;
+    for (int v = v0 + tid; v < v1; v += 256) {
+        const float x = lg[v];
+        if (x > m) {
+            z = ts_rescale(z, m, x) + 1.f;
+            m = x;
+        } else if (x == x && x != -INFINITY) {
+            z += expf(x - m);
+        }
+    }
+    beam_wave_lse(m, z);
+    if (lane == 0) {
+        s_m[wave] = m;
+        s_s[wave] = z;
+    }
+    // every wave's K best ids, in order: round r takes the best id that ranks after round r - 1's (the chunk stays in L1 / L2)
+    float pv = 0.f;
+    int pi = -1;
+    for (int r = 0; r < K; ++r) {
+        float bv = -INFINITY;
+        int bi = BEAM_NONE;
+        for (int v = v0 + tid; v < v1; v += 256) {
+            float x = lg[v];
+            const uint8_t mk = p.mask[v];
+            if ((mk & 1) || ((mk & 2) && at_begin)) x = -INFINITY;
+            if ((r == 0 || argmax_better(pv, pi, x, v)) && argmax_better(x, v, bv, bi)) {
+                bv = x;
+                bi = v;
+            }
+        }
+        beam_wave_best(bv, bi);
+        if (lane == 0) {
+            s_v[wave][r] = bv;
+            s_i[wave][r] = bi;
+        }
+        pv = bv;
+        pi = bi;
+        if (bi == BEAM_NONE) {   // wave-uniform: the wave's ids are used up
+            if (lane == 0)
+                for (int k = r + 1; k < K; ++k) s_i[wave][k] = BEAM_NONE;
+            break;
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    // the four sorted lists, one candidate per lane, merged into the chunk's K best
+    const int w = lane / BEAM_KMAX, k = lane % BEAM_KMAX;
+    float cv = -INFINITY;
+    int ci = BEAM_NONE;
+    if (k < K) {
+        cv = s_v[w][k];
+        ci = s_i[w][k];
+    }
+    float M = lane < 4 ? s_m[lane] : -INFINITY, Z = lane < 4 ? s_s[lane] : 0.f;
+    beam_wave_lse(M, Z);
+    BeamPart* out = p.beam.part + (size_t)b * SELECT_CHUNKS + chunk;
+    if (lane == 0) {
+        out->m = M;
+        out->s = Z;
+    }
+    for (int r = 0; r < K; ++r) {
+        float bv = ci == BEAM_NONE ? -INFINITY : cv;
+        int bi = ci;
+        beam_wave_best(bv, bi);
+        if (bi != BEAM_NONE && bi == ci) ci = BEAM_NONE;   // taken
+        if (lane == 0) {
+            out->val[r] = bv;
+            out->idx[r] = bi == BEAM_NONE ? -1 : bi;
+        }
+    }
+}
+
+// BeamHypotheses.add for utterance u (a whole wave calls it; lane 0 keeps the books, every lane copies ids): `sum` = the candidate's
+// sum of log-probabilities, `src` = the hypothesis' ids (length len, the EOS not included)
+__device__ __forceinline__ void beam_hyp_add(const BeamParams& bp, const int u, const int* src, const int len, const float sum, const int lane) {
+    int slot = -1;
+    if (lane == 0) {
+        const int nb = bp.nb;
+        const double score = (double)sum / pow((double)len, (double)bp.length_penalty);
+        const int n = bp.hyp_n[u];
+        const double worst = bp.hyp_worst[u];
+        double* hs = bp.hyp_score + (size_t)u * nb;
+        if (n < nb) {
+            slot = n;
+            bp.hyp_n[u] = n + 1;
+            bp.hyp_worst[u] = score < worst ? score : worst;
+        } else if (score > worst) {   // the worst kept hypothesis leaves; the new worst is the smallest of the rest and the newcomer
+            int lo = 0;
+            for (int k = 1; k < nb; ++k)
+                if (hs[k] < hs[lo]) lo = k;
+            double nw = score;
+            for (int k = 0; k < nb; ++k)
+                if (k != lo && hs[k] < nw) nw = hs[k];
+            slot = lo;
+            bp.hyp_worst[u] = nw;
+        }
+        if (slot >= 0) {
+            hs[slot] = score;
+            bp.hyp_len[u * nb + slot] = len;
+        }
+    }
+    slot = __shfl(slot, 0);
+    if (slot < 0) return;
+    int* dst = bp.hyp_ids + ((size_t)u * bp.nb + slot) * bp.hyp_ld;
+    for (int i = lane; i < len; i += 64) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(256) void beam_finish_kernel(const SelectParams p) {
+    __shared__ int s_tok[MAX_ROWS];
+    __shared__ int s_pos[MAX_ROWS];
+    __shared__ int s_unf[MAX_ROWS];
+    __shared__ int s_src[MAX_ROWS];     // the row whose history row b continues
+    __shared__ float s_sc[MAX_ROWS];
+    __shared__ float s_tv[4][BEAM_KMAX];
+    __shared__ int s_tf[4][BEAM_KMAX];
+    DecState* st = p.st;
+    const BeamParams& bp = p.beam;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = bp.nb, U = bp.U, K = 2 * nb, R = p.B;
+    // the rows of a wt_decoder_begin batch stay aligned: row 0's counters are everybody's
+    const int done = st->done, cur_len = st->cur_len[0], step = st->step, pos = st->pos[0], self_len = st->self_len[0], seq = st->seq + 1,
+              epoch = st->epoch;
+    if (done) {         // block-uniform: steps enqueued past the stop test are no-ops (the host still sees them retire)
+        if (tid == 0) {
+            st->seq = seq;
+            unsigned unf_mask = 0;
+            for (int r = 0; r < R; ++r) unf_mask |= p.unfinished[r] ? 1u << r : 0u;
+            if (p.mailbox) __hip_atomic_store(p.mailbox, mailbox_word(epoch, seq, 1, cur_len, unf_mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        return;
+    }
+    const int forced = p.forced[cur_len];                          // ForceTokensLogitsProcessor: 0 at the forced id, -inf elsewhere
+    const int par = step & 1;
+    const int* ids_cur = par ? bp.ids2 : p.ids;
+    int* ids_nxt = par ? p.ids : bp.ids2;
+    const int* anc_cur = bp.anc + (size_t)par * MAX_ROWS * bp.anc_ld;
+    int* anc_nxt = bp.anc + (size_t)(par ^ 1) * MAX_ROWS * bp.anc_ld;
+    for (int u = wave; u < U; u += 4) {   // wave-uniform
+        const int r0 = u * nb;
+        if (bp.hyp_done[u]) {   // a finished utterance's rows are padded
+            if (lane < nb) {
+                s_tok[r0 + lane] = p.pad;
+                s_src[r0 + lane] = r0 + lane;
+                s_sc[r0 + lane] = 0.f;
+                s_unf[r0 + lane] = 0;
+            }
+            if (bp.dbg_cand && lane < BEAM_KMAX) bp.dbg_cand[(u * BEAM_KMAX + lane) * 3] = -1;
+            continue;
+        }
+        // lane j keeps beam j's log-sum-exp and running score
+        float my_lse = 0.f;
+        const float my_bs = bp.scores[r0 + min(lane, nb - 1)];
+        for (int j = 0; j < nb; ++j) {
+            float m = -INFINITY, z = 0.f;
+            if (lane < SELECT_CHUNKS) {
+                const BeamPart* q = bp.part + (size_t)(r0 + j) * SELECT_CHUNKS + lane;
+                m = q->m;
+                z = q->s;
+            }
+            beam_wave_lse(m, z);
+            if (lane == j) my_lse = m + logf(z);
+        }
+        // the utterance's nb * SELECT_CHUNKS * K candidates, up to 16 per lane: score and flat index beam * V + id
+        const int n_c = nb * SELECT_CHUNKS * K;
+        float cv[16];
+        int cf[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int c = lane + 64 * i;
+            const int j = min(forced >= 0 ? c : c / (SELECT_CHUNKS * K), nb - 1);
+            const float lse_j = __shfl(my_lse, j), bs_j = __shfl(my_bs, j);
+            cv[i] = -INFINITY;
+            cf[i] = BEAM_NONE;
+            if (forced >= 0) {
+                if (c < nb) {
+                    cv[i] = 0.f + bs_j;
+                    cf[i] = c * p.V + forced;
+                }
+            } else if (c < n_c) {
+                const int rem = c - j * (SELECT_CHUNKS * K);
+                const BeamPart* q = bp.part + (size_t)(r0 + j) * SELECT_CHUNKS + rem / K;
+                const int idx = q->idx[rem % K];
+                if (idx >= 0) {
+                    cv[i] = (q->val[rem % K] - lse_j) + bs_j;
+                    cf[i] = j * p.V + idx;
+                }
+            }
+        }
+        unsigned taken = 0;
+        for (int r = 0; r < K; ++r) {
+            float bv = -INFINITY;
+            int bf = BEAM_NONE;
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (!((taken >> i) & 1u) && cf[i] != BEAM_NONE && argmax_better(cv[i], cf[i], bv, bf)) {
+                    bv = cv[i];
+                    bf = cf[i];
+                }
+            beam_wave_best(bv, bf);
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+                if (bf != BEAM_NONE && cf[i] == bf) taken |= 1u << i;
+            if (lane == 0) {
+                s_tv[wave][r] = bv;
+                s_tf[wave][r] = bf;
+                if (bp.dbg_cand) {
+                    int* dc = bp.dbg_cand + (u * BEAM_KMAX + r) * 3;
+                    dc[0] = bf == BEAM_NONE ? -1 : bf % p.V;
+                    dc[1] = bf == BEAM_NONE ? -1 : bf / p.V;
+                    dc[2] = __float_as_int(bv);
+                }
+            }
+        }
+        if (bp.dbg_cand && lane >= K && lane < BEAM_KMAX) bp.dbg_cand[(u * BEAM_KMAX + lane) * 3] = -1;
+        __builtin_amdgcn_wave_barrier();
+        // BeamSearchScorer.process
+        int bi = 0;
+        for (int r = 0; r < K && bi < nb; ++r) {
+            const float sc = s_tv[wave][r];
+            const int f = s_tf[wave][r];
+            if (f == BEAM_NONE) break;
+            const int j = f / p.V, tok = f - j * p.V;
+            if (tok == p.eos) {
+                if (r >= nb) continue;   // an EOS below the top nb is dropped
+                beam_hyp_add(bp, u, ids_cur + (size_t)(r0 + j) * p.max_length, cur_len, sc, lane);
+            } else {
+                if (lane == 0) {
+                    s_tok[r0 + bi] = tok;
+                    s_src[r0 + bi] = r0 + j;
+                    s_sc[r0 + bi] = sc;
+                }
+                ++bi;
+            }
+        }
+        for (; bi < nb; ++bi)   // fewer than nb continuations (the reference raises): the row dies with a score of -inf
+            if (lane == 0) {
+                s_tok[r0 + bi] = p.pad;
+                s_src[r0 + bi] = r0 + bi;
+                s_sc[r0 + bi] = -INFINITY;
+            }
+        int udone = 0;
+        if (lane == 0) {   // BeamHypotheses.is_done(best candidate score of the step, cur_len + 1)
+            if (bp.hyp_n[u] >= nb) {
+                if (bp.early_stopping) udone = 1;
+                else udone = bp.hyp_worst[u] >= (double)s_tv[wave][0] / pow((double)(cur_len + 1), (double)bp.length_penalty);
+            }
+            bp.hyp_done[u] = udone;
+        }
+        udone = __shfl(udone, 0);
+        if (lane < nb) s_unf[r0 + lane] = !udone;
+    }
+    __syncthreads();
+    // every row: re-parent the id history and the ancestry table into the other buffer, append the token
+    for (int i = tid; i < R * cur_len; i += 256) {
+        const int b = i / cur_len, c = i - b * cur_len;
+        ids_nxt[(size_t)b * p.max_length + c] = ids_cur[(size_t)s_src[b] * p.max_length + c];
+    }
+    for (int i = tid; i < R * self_len; i += 256) {
+        const int b = i / self_len, c = i - b * self_len;
+        anc_nxt[(size_t)b * bp.anc_ld + c] = anc_cur[(size_t)s_src[b] * bp.anc_ld + c];
+    }
+    if (tid < R) {
+        const int b = tid;
+        ids_nxt[(size_t)b * p.max_length + cur_len] = s_tok[b];
+        anc_nxt[(size_t)b * bp.anc_ld + self_len] = s_src[b];            // this step's key was appended to the source row
+        if (self_len + 1 < bp.anc_ld) anc_nxt[(size_t)b * bp.anc_ld + self_len + 1] = b;   // the next step's key goes to the row itself
+        bp.scores[b] = s_sc[b];
+        p.unfinished[b] = s_unf[b];
+        s_pos[b] = pos + 1;
+        st->cur_len[b] = cur_len + 1;
+        st->pos[b] = pos + 1;
+        st->self_len[b] = self_len + 1;
+        if (bp.trace) {
+            int* tr = bp.trace + ((size_t)step * R + b) * 4;
+            tr[0] = s_tok[b];
+            tr[1] = s_src[b] - (b / nb) * nb;
+            tr[2] = __float_as_int(s_sc[b]);
+            tr[3] = !s_unf[b];
+        }
+    }
+    if (tid == 0) {
+        int nu = 0;
+        unsigned unf_mask = 0;
+        for (int r = 0; r < R; ++r)
+            if (s_unf[r]) {
+                ++nu;
+                unf_mask |= 1u << r;
+            }
+        st->n_unfinished = nu;
+        st->step = step + 1;
+        const int now_done = nu == 0 || cur_len + 1 >= p.max_length;   // beam_scorer.is_done or MaxLengthCriteria
+        if (now_done) st->done = 1;
+        st->seq = seq;
+        if (p.mailbox) __hip_atomic_store(p.mailbox, mailbox_word(epoch, seq, now_done, cur_len + 1, unf_mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (!p.next_x || cur_len + 1 >= p.max_length) return;
+    __syncthreads();   // s_pos
+    finish_embed(p, s_tok, s_pos, tid);
+}
+
+__global__ __launch_bounds__(256) void beam_finalize_kernel(const SelectParams p) {
+    __shared__ int s_pick[2];
+    __shared__ float s_score;
+    const BeamParams& bp = p.beam;
+    const DecState* st = p.st;
+    const int u = blockIdx.x, tid = threadIdx.x, nb = bp.nb, cur_len = st->cur_len[0];
+    const int* ids_cur = (st->step & 1) ? bp.ids2 : p.ids;
+    if (tid == 0) {   // a copy of the utterance's store, joined by its open beams unless it is done (the store itself is left alone)
+        double sc[MAX_BEAMS];
+        int src[MAX_BEAMS], len[MAX_BEAMS];
+        int n = bp.hyp_n[u];
+        double worst = bp.hyp_worst[u];
+        for (int k = 0; k < n; ++k) {
+            sc[k] = bp.hyp_score[(size_t)u * nb + k];
+            src[k] = k;
+            len[k] = bp.hyp_len[u * nb + k];
+        }
+        if (!bp.hyp_done[u])
+            for (int j = 0; j < nb; ++j) {
+                const double score = (double)bp.scores[u * nb + j] / pow((double)cur_len, (double)bp.length_penalty);
+                int slot = -1;
+                if (n < nb) {
+                    slot = n++;
+                    worst = score < worst ? score : worst;
+                } else if (score > worst) {
+                    int lo = 0;
+                    for (int k = 1; k < nb; ++k)
+                        if (sc[k] < sc[lo]) lo = k;
+                    worst = score;
+                    for (int k = 0; k < nb; ++k)
+                        if (k != lo && sc[k] < worst) worst = sc[k];
+                    slot = lo;
+                }
+                if (slot >= 0) {
+                    sc[slot] = score;
+                    src[slot] = nb + j;
+                    len[slot] = cur_len;
+                }
+            }
+        int best = 0;   // (exactly equal scores: the highest slot; the reference's choice there is its sort's, whisper_trtllm_amd.h (9c))
+        for (int k = 1; k < n; ++k)
+            if (sc[k] >= sc[best]) best = k;
+        s_pick[0] = n > 0 ? src[best] : nb;
+        s_pick[1] = n > 0 ? len[best] : cur_len;
+        s_score = n > 0 ? (float)sc[best] : 0.f;
+    }
+    __syncthreads();
+    const int pick = s_pick[0], len = s_pick[1];
+    const int* src = pick < nb ? bp.hyp_ids + ((size_t)u * nb + pick) * bp.hyp_ld : ids_cur + (size_t)(u * nb + pick - nb) * p.max_length;
+    int* row = bp.out_ids + (size_t)u * p.max_length;
+    for (int i = tid; i < p.max_length; i += 256) row[i] = i < len ? src[i] : i == len ? p.eos : p.pad;
+    if (tid == 0) bp.out_scores[u] = s_score;
+}
+
+__global__ void beam_init_kernel(const SelectParams p) {
+    const BeamParams& bp = p.beam;
+    const int t = threadIdx.x;
+    if (t < MAX_ROWS) {
+        bp.urow[t] = min(t / bp.nb, bp.U - 1);
+        bp.anc[(size_t)t * bp.anc_ld] = t;
+        if (t < p.B) bp.scores[t] = t % bp.nb == 0 ? 0.f : -1e9f;
+    }
+    if (t < bp.U) {
+        bp.hyp_n[t] = 0;
+        bp.hyp_done[t] = 0;
+        bp.hyp_worst[t] = 1e9;
+    }
+}
+static bool beam_params_ok(const SelectParams& p) {
+    const BeamParams& b = p.beam;
+    return b.nb >= 2 && b.nb <= MAX_BEAMS && b.U >= 1 && b.U * b.nb == p.B && p.B <= MAX_ROWS && !p.fused && !p.stream && !p.ts_on && !p.trace &&
+           b.part && b.scores && b.ids2 && b.anc && b.urow && b.hyp_n && b.hyp_done && b.hyp_worst && b.hyp_score && b.hyp_len && b.hyp_ids &&
+           b.out_ids && b.out_scores && b.hyp_ld >= p.max_length && b.anc_ld >= p.max_length && p.V >= 1 && (long long)b.nb * p.V < BEAM_NONE;
+}
+hipError_t launch_beam_init(const SelectParams& p, hipStream_t s) {
+    if (!beam_params_ok(p)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(beam_init_kernel, dim3(1), dim3(64), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_beam_finalize(const SelectParams& p, hipStream_t s) {
+    if (!beam_params_ok(p)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(beam_finalize_kernel, dim3(p.beam.U), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     if (p.B > MAX_ROWS || p.n_parts < 1 || (!p.fused && p.n_parts != SELECT_CHUNKS)) return hipErrorInvalidValue;
     if (p.stream && (!p.host_ids || !p.host_len || p.trace)) return hipErrorInvalidValue;
+    if (p.beam_on) {   // beam search: batch decodes only, over logits in HBM
+        if (!beam_params_ok(p)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(beam_select_kernel, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(beam_finish_kernel, dim3(1), dim3(256), 0, s, p);
+        return hipGetLastError();
+    }
     if (p.ts_on) {   // timestamp mode: batch decodes only, over logits in HBM
         if (p.fused || p.stream || !p.ts_part || p.tb <= 0 || p.tb >= p.V || p.no_ts < 0 || p.no_ts >= p.tb || p.ts_begin_index < 2)
             return hipErrorInvalidValue;

@@ -131,6 +131,13 @@ struct DecAttnParams {
     const int* alive;      // optional [B]: rows with alive[b] == 0 (finished: they emit pad whatever their logits) stream no K/V; their
                            // context / partials keep the previous step's (finite) values.  nullptr: every row attends.
     const int* slot_row;   // optional [B] (continuous mode, cross attention): slot b reads cache row max(slot_row[b], 0) instead of row b
+    // beam search, self attention: key s of row b lives in physical cache row anc[(parity * MAX_ROWS + b) * anc_ld + s], parity =
+    // st->step & 1 (0 without st): the ancestry table beam_finish_kernel maintains instead of regathering the caches.  Unsplit only.
+    const int* anc;
+    int anc_ld;
+    // beam search, cross attention, grouped form (2 or 4; 0 / 1: off): cache row u is shared by the query rows u * group .. + group - 1,
+    // one block streams it once for all of them (grid z = B / group).  Not with slot_row / alive / anc.
+    int group;
 };
 
 // A/B tuning switches (WT_NSPLIT_CROSS, WT_GEMM_NO_DMA, ...; DESIGN.md "Tuning knobs") are lab tools, not part of the C-ABI's
@@ -227,6 +234,44 @@ struct TsPart {
     int pad[2];
 };
 
+// Beam search (wt_decoder_set_beam_search): rows are [utterance][beam], row = u * nb + j.
+constexpr int MAX_BEAMS = 8;
+constexpr int BEAM_KMAX = 2 * MAX_BEAMS;   // candidates kept per utterance and step: 2 * num_beams
+// One vocabulary chunk of one row (beam_select_kernel -> beam_finish_kernel): the online log-sum-exp pair over ALL ids of the chunk
+// (m = largest non-NaN logit, s = sum of exp(x - m); NaN logits are left out of it) and the chunk's 2 * nb best ids under the
+// suppress masks (masked: -inf), NaN-aware, lowest index on ties; idx < 0: the chunk holds fewer ids than that.
+struct BeamPart {
+    float m, s;
+    float val[BEAM_KMAX];
+    int idx[BEAM_KMAX];
+    int pad[2];
+};
+// Device state of a beam decode.  The id history and the ancestry table are double-buffered on the parity of DecState.step: a step
+// reads buffer step & 1 and beam_finish_kernel writes the re-parented rows into the other one.
+struct BeamParams {
+    int nb, U;                 // beams per utterance, utterances (rows B = U * nb)
+    float length_penalty;
+    int early_stopping;
+    BeamPart* part;            // [B][SELECT_CHUNKS]
+    float* scores;             // [B] running beam scores (sum of log-probabilities)
+    int* ids2;                 // [B][max_length]: id buffer of odd steps (SelectParams.ids: even steps)
+    int* anc;                  // [2][MAX_ROWS][anc_ld]: physical self-cache row of key s of row b
+    int anc_ld;
+    int* urow;                 // [MAX_ROWS]: row -> utterance (the cross-attention's slot_row table)
+    // BeamHypotheses per utterance: nb entries of (score, length, ids), the worst kept score, the done flag
+    int* hyp_n;                // [U]
+    int* hyp_done;             // [U]
+    double* hyp_worst;         // [U]
+    double* hyp_score;         // [U][nb]
+    int* hyp_len;              // [U][nb]
+    int* hyp_ids;              // [U][nb][hyp_ld]
+    int hyp_ld;
+    int* out_ids;              // [U][max_length]: finalize's best hypothesis (EOS behind it when it fits, then pad)
+    float* out_scores;         // [U]
+    int* trace;                // optional [max_length][B][4]: per step and row (token, source beam within the utterance, score bits, done)
+    int* dbg_cand;             // optional (debug hook) [U][BEAM_KMAX][3]: the sorted candidates (token, source beam, score bits), token -1 = none
+};
+
 struct SelectParams {
     const float* logits;   // [B][V]
     const uint8_t* mask;   // [V] bit0: always suppressed, bit1: suppressed when cur_len == begin_index
@@ -257,8 +302,13 @@ struct SelectParams {
     TsPart* ts_part;                 // scratch [B][SELECT_CHUNKS]
     int* ts_tok;                     // optional [B]: the rule-chosen token before the forced / pad / EOS bookkeeping (debug hook)
     float* ts_stats;                 // optional [B][2]: (log-sum-exp of the timestamp scores, text maximum) after the masks (debug hook)
+    // beam search (beam_on != 0; wt_decoder_set_beam_search): plain logits in HBM, then beam_select_kernel + beam_finish_kernel
+    int beam_on;
+    BeamParams beam;
 };
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s);
+hipError_t launch_beam_init(const SelectParams& p, hipStream_t s);       // beam scores 0 / -1e9, identity ancestry, empty hypothesis stores
+hipError_t launch_beam_finalize(const SelectParams& p, hipStream_t s);   // BeamSearchScorer.finalize into beam.out_ids / out_scores (idempotent)
 hipError_t launch_dec_init(DecState* st, int* ids, int* unfinished, int B, int max_length, int start_token, int epoch, hipStream_t s);
 // continuous mode: empty slots, empty queue
 hipError_t launch_stream_init(DecState* st, int* unfinished, int B, int epoch, hipStream_t s);

@@ -209,6 +209,16 @@ def timestamp_rules(config: dict):
     return int(no_ts), int(no_ts) + 1, ts_begin, -1 if max_init is None else int(max_init), kept
 
 
+def _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps):
+    """The combinations the engine refuses (wt_decoder_begin: WT_E_UNSUPPORTED), refused before anything is enqueued."""
+    if not isinstance(num_beams, int) or num_beams < 1 or num_beams > 8:
+        raise ValueError(f"num_beams must be an integer in [1, 8], got {num_beams!r}")
+    if num_beams > 1 and return_timestamps:
+        raise ValueError("beam search and timestamp mode cannot be combined (num_beams > 1 with return_timestamps=True)")
+    if num_beams > 1 and (logits_trace is not None or force_eos_step is not None or force_eos_steps is not None):
+        raise ValueError("beam search does not take logits_trace / force_eos_step(s)")
+
+
 class WhisperDecoderEngine:
     """Greedy decode with the KV cache resident on the device (no per-token host round trip).
 
@@ -263,11 +273,23 @@ class WhisperDecoderEngine:
         _lib.check(self.session._lib.wt_decoder_set_timestamp_rules(self.session.handle, ctypes.byref(t) if t is not None else None),
                    "wt_decoder_set_timestamp_rules")
 
+    def _set_beam_search(self, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False):
+        b = None
+        if num_beams > 1:
+            if early_stopping not in (False, True):
+                raise ValueError(f"early_stopping must be False or True, got {early_stopping!r} (\"never\" is not supported)")
+            b = _lib.BeamParams(int(num_beams), float(length_penalty), int(bool(early_stopping)))
+        _lib.check(self.session._lib.wt_decoder_set_beam_search(self.session.handle, ctypes.byref(b) if b is not None else None),
+                   "wt_decoder_set_beam_search")
+
     def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
-              return_timestamps: bool = False):
+              return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False):
         """Start a decode (wt_decoder_begin).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
-        the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s)."""
+        the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
+        `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
+        (False or True); utterances x num_beams <= 16 rows per call; not together with timestamps, logits_trace or force_eos_step(s)."""
         import torch
+        _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps)
         i = self.session.info
         if encoder_hidden.dtype != torch.float32 or tuple(encoder_hidden.shape[1:]) != (i.max_source_positions, i.d_model):
             raise ValueError(f"encoder_hidden must be float32 [B,{i.max_source_positions},{i.d_model}]")
@@ -280,6 +302,8 @@ class WhisperDecoderEngine:
         self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps)
         self._trace = logits_trace
         self._set_timestamp_rules(return_timestamps)
+        self._set_beam_search(num_beams, length_penalty, early_stopping)
+        self._beams = int(num_beams) if num_beams > 1 else 1
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.session._lib.wt_decoder_begin(self.session.handle, self._enc.data_ptr(), self._B, ctypes.byref(self._p),
                                                        ctypes.c_void_p(stream)), "wt_decoder_begin")
@@ -314,15 +338,63 @@ class WhisperDecoderEngine:
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.session._lib.wt_decoder_read_ids(self.session.handle, buf.data_ptr(), ml, ctypes.c_void_p(stream)),
                    "wt_decoder_read_ids")
+        if getattr(self, "_beams", 1) > 1:
+            # the best hypothesis per utterance, EOS behind it when it fits, then pad: the width of BeamSearchScorer.finalize is
+            # min(longest hypothesis + 1, max_length).  A hypothesis never holds the EOS id itself (an EOS candidate ends its beam).
+            # (int(lens.max()) below waits for the copy: the C call itself stays stream-ordered, this width does not)
+            is_eos = buf[:, 1:] == self._p.eos_token_id
+            lens = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, torch.full_like(buf[:, 0], ml))
+            return buf[:, :min(int(lens.max()) + 1, ml)].clone()
         return buf[:, :cur_len].clone()
 
+    def read_beam_scores(self):
+        """Sequence scores of the beam decode in flight (sum of log-probabilities / length ** length_penalty), float32 [B] on the GPU."""
+        import torch
+        out = torch.empty(self._B, dtype=torch.float32, device=self._enc.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_decoder_read_beam_scores(self.session.handle, out.data_ptr(), ctypes.c_void_p(stream)),
+                   "wt_decoder_read_beam_scores")
+        return out
+
+    def beam_trace(self, steps: int):
+        """Debug read-back of a beam decode: int32 [steps, rows, 4] = (token, source beam within the utterance, score bits, done)."""
+        import torch
+        out = torch.empty(steps, self._B * self._beams, 4, dtype=torch.int32, device=self._enc.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_dbg_beam_trace(self.session.handle, out.data_ptr(), steps, ctypes.c_void_p(stream)), "wt_dbg_beam_trace")
+        return out
+
     def generate(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, chunk: int = 0, force_eos_steps=None,
-                 lookahead: int = 0, return_timestamps: bool = False):
+                 lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping=False, return_scores: bool = False):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
-        `return_timestamps`: timestamp mode (see `begin`).
+        `return_timestamps`: timestamp mode (see `begin`).  `num_beams` > 1: beam search (see `begin`), the best hypothesis per
+        utterance; `return_scores`: (ids, float32 sequence scores [B]) -- beam search only.
 
         Default (`chunk` 0): the stop test is followed through the engine's host mailbox (`run`), at most `lookahead` steps are
         enqueued past the stop.  `chunk` > 0 selects the older protocol -- `chunk` steps between two synchronising polls."""
+        _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps)
+        if return_scores and num_beams <= 1:
+            raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence score)")
+        group = self.max_batch // max(int(num_beams), 1)
+        if num_beams > 1 and encoder_hidden.shape[0] > group:   # utterances x beams <= 16 rows per engine call
+            import torch
+            parts = [self.generate(encoder_hidden[i:i + group], max_length, None, None, chunk, None, lookahead, False, num_beams,
+                                   length_penalty, early_stopping, True) for i in range(0, encoder_hidden.shape[0], group)]
+            width = max(p[0].shape[1] for p in parts)
+            ids = torch.cat([torch.nn.functional.pad(p[0], (0, width - p[0].shape[1]), value=self.config["pad_token_id"]) for p in parts], dim=0)
+            return (ids, torch.cat([p[1] for p in parts])) if return_scores else ids
+        if num_beams > 1:
+            self.begin(encoder_hidden, max_length, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
+            if chunk <= 0:
+                cur, _nu = self.run(lookahead)
+            else:
+                cur, done, ml = 1, False, self._p.max_length
+                while not done and cur < ml:
+                    self.steps(min(chunk, ml - cur))
+                    cur, _nu, done = self.poll()
+            ids = self.read_ids(cur)
+            return (ids, self.read_beam_scores()) if return_scores else ids
         if encoder_hidden.shape[0] > self.max_batch:
             # larger batches run as consecutive engine batches of <= 16 utterances;
             # rows are independent, so the result is the concatenation (shorter groups are right-padded with pad_token_id)
@@ -348,12 +420,14 @@ class WhisperDecoderEngine:
             cur, _nu, done = self.poll()
         return self.read_ids(cur)
 
-    def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False) -> "DecodeStream":
+    def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1) -> "DecodeStream":
         """Open a continuous decode on this engine (wt_decoder_stream_*): `slots` rows stay busy, every utterance stops at its own EOS
         and its slot is refilled on the device within the same step.  Ends with the next `begin` / `generate` on this engine.
         The continuous mode has no timestamp mode: `return_timestamps=True` raises ValueError."""
         if return_timestamps:
             raise ValueError("timestamp mode is a batch-decode feature (generate / begin); the continuous mode does not predict timestamps")
+        if num_beams > 1:
+            raise ValueError("beam search is a batch-decode feature (generate / begin); the continuous mode decodes greedily")
         return DecodeStream(self, slots, pool_rows, max_length)
 
     def set_profiling(self, enabled: bool):
@@ -402,6 +476,7 @@ class DecodeStream:
         self._p = dec._params(max_length, None, None)
         self.max_length = int(self._p.max_length)
         dec._set_timestamp_rules(False)     # a timestamp decode before on this handle left the mode on
+        dec._set_beam_search(1)             # ... and so did a beam decode
         self.pool_rows = int(pool_rows) if pool_rows else 4 * self.slots
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_decoder_stream_begin(self._h, self.slots, self.pool_rows, ctypes.byref(self._p), ctypes.c_void_p(stream)),
@@ -468,7 +543,7 @@ class DecodeStream:
 
 def transcribe_continuous(enc: "WhisperEncoderEngine", dec: "WhisperDecoderEngine", mels, slots: int = 8, chunk: int = 8,
                           force_eos_steps: Optional[Sequence[int]] = None, max_length=None, stats: Optional[dict] = None,
-                          pool_rows: int = 0, return_timestamps: bool = False) -> List[Any]:
+                          pool_rows: int = 0, return_timestamps: bool = False, num_beams: int = 1) -> List[Any]:
     """Encoder + continuous greedy decode of `mels` ([N, n_mels, 2*S] tensor or a list of such rows) in ARRIVAL order: the encoder runs
     on chunks of `chunk` utterances just ahead of the decode, `slots` rows decode at any time.  Returns N numpy id rows (start token
     through EOS) in input order.  This is the host scheduler of the C-ABI's continuous mode -- what cal_wer.py / run.py use for a
@@ -476,6 +551,8 @@ def transcribe_continuous(enc: "WhisperEncoderEngine", dec: "WhisperDecoderEngin
     import torch
     if return_timestamps:
         raise ValueError("timestamp mode is a batch-decode feature (WhisperDecoderEngine.generate); the continuous mode does not predict timestamps")
+    if num_beams > 1:
+        raise ValueError("beam search is a batch-decode feature (WhisperDecoderEngine.generate); the continuous mode decodes greedily")
     n = len(mels)
     results: List[Any] = [None] * n
     if n == 0:
