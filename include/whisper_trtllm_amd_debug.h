@@ -33,7 +33,8 @@ int wt_dbg_layernorm(const float* x, const float* w, const float* b, float* y, i
 int wt_dbg_encoder_attention(const float* qkv, float* ctx, int B, int S, int H, void* stream);
 /* same with fp16 qkv / ctx (fp32 scores, softmax and accumulators) */
 int wt_dbg_encoder_attention_f16(const void* qkv, void* ctx, int B, int S, int H, void* stream);
-/* Y[B][N] = act((X' W^T + bias) * scale) (+ resid); xmode 0: X'=X[B][K], 1: X'=LayerNorm(X) */
+/* Y[B][N] = act((X' W^T + bias) * scale) (+ resid); xmode 0: X'=X[B][K], 1: X'=LayerNorm(X).  This hook (and wt_dbg_skinny_f16) covers
+ * the plain epilogue (YMODE_PLAIN) only: the argmax epilogue is wt_dbg_vocab_argmax's, the q|k|v cache append wt_dbg_skinny_qkv_append's. */
 int wt_dbg_skinny(const float* X, const float* ln_w, const float* ln_b, const float* W, const float* bias,
                   const float* resid, float* Y, int B, int N, int K, int xmode, int act, float scale, void* stream);
 /* q [B][H*64] (pre-scaled), k/v cache [B][H][s_cap][64] with the first `len` rows valid -> out [B][H*64];
@@ -148,6 +149,48 @@ int wt_dbg_beam_logits(wt_engine* dec, float* logits_out, void* stream);
 /* a beam decode in flight: per executed step and row (token, source beam within the utterance, score bits, utterance done), device int32
  * [steps][rows][4] */
 int wt_dbg_beam_trace(wt_engine* dec, int32_t* trace_out, int steps, void* stream);
+
+/* ---- the greedy step's fused launches (tests/test_gpu_select.py), parameterised by the helpers the engine itself launches through
+ * (wt_common.h).  Host arrays (`cur_len`, `self_len`, `forced`, `state`, ...) are uploaded into `scratch`; these calls synchronise `stream`. */
+/* The vocabulary GEMV, logits[b][n] = X'[b] . W[n] (+ bias[n]): X [B][K] (K % 8 == 0, K <= 1024; xmode 1: LayerNorm with ln_w / ln_b first,
+ * as the engine; 0: plain), W [N][K] float or IEEE half (w_half), bias [N] or NULL, w_nt: non-temporal weight loads.
+ * fused != 0: the argmax epilogue.  mask bytes [N] (bit 0: suppressed, bit 1: suppressed on rows with cur_len[b] == begin_index), cur_len a
+ *   HOST array [B]; every workgroup leaves its masked (max, argmax) per row -- torch.argmax semantics: NaN is the maximum, lowest index on
+ *   ties -- in part_val / part_idx [B][parts], parts = wt_dbg_vocab_argmax_parts(B, N, K, w_half) (the launch's workgroup count; workgroup
+ *   g owns the rows [g * rpw, (g + 1) * rpw) with rpw = ceil(N / parts) rounded up to the plan's row-group multiple, see the test);
+ *   `logits` [B][N] or NULL receives the raw (unmasked) logits, the engine's logits_trace.
+ * fused == 0: the plain epilogue the unfused path uses: `logits` [B][N] is the output, mask / parts are not touched.
+ * scratch: wt_dbg_vocab_argmax_scratch_bytes() bytes. */
+int wt_dbg_vocab_argmax_parts(int B, int N, int K, int w_half);
+size_t wt_dbg_vocab_argmax_scratch_bytes(void);
+int wt_dbg_vocab_argmax(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, const unsigned char* mask,
+                        const int32_t* cur_len, int begin_index, int B, int N, int K, int xmode, int w_half, int w_nt, int fused, float* logits,
+                        float* part_val, int32_t* part_idx, void* scratch, void* stream);
+/* LayerNorm + fused q|k|v projection of a decoder layer: X [B][d], W [3d][d] float or half, bias [3d] -> q [B][d] = scale * (first third);
+ * the k / v thirds are written at sequence row self_len[b] (HOST array [B], 0 <= self_len[b] < s_cap, one position PER ROW) of the caches
+ * [B][d / 64][s_cap][64], float or IEEE half (kv_half); nothing else of the caches is written.
+ * scratch: wt_dbg_skinny_qkv_append_scratch_bytes() bytes. */
+size_t wt_dbg_skinny_qkv_append_scratch_bytes(void);
+int wt_dbg_skinny_qkv_append(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* q, void* kcache,
+                             void* vcache, const int32_t* self_len, int B, int d, int s_cap, int w_half, int kv_half, int w_nt, float scale,
+                             void* scratch, void* stream);
+/* The plain greedy tail as the engine enqueues it: greedy_select_kernel over logits [B][V] (part_val / part_idx NULL), or, with logits NULL,
+ * the fused form over precomputed partials part_val / part_idx [B][n_parts] (the vocabulary GEMV's); then greedy_finish_kernel<false>.
+ * mask bytes [V] (device), forced a HOST array [max_length] (forced token of sequence index i, < 0: none), ids int32 [B][max_length] and
+ * unfinished int32 [B] (device, updated in place), force_eos_step (< 0: off) / force_eos_rows (HOST [B] or NULL) the two forced-EOS forms.
+ * state: HOST int32 [52] in and out = DecState's {done, n_unfinished, step, seq, cur_len[16], pos[16], self_len[16]}; 1 <= cur_len[b] <
+ * max_length.  next_x [B][d] (or NULL) = tok_emb[token] + pos_emb[pos[0] + 1], tok_emb [V][d] float or half (emb_half), pos_emb
+ * [pos_rows][d].  No mailbox.  scratch: wt_dbg_greedy_select_scratch_bytes(max_length) bytes. */
+size_t wt_dbg_greedy_select_scratch_bytes(int max_length);
+int wt_dbg_greedy_select(const float* logits, const float* part_val, const int32_t* part_idx, int n_parts, const unsigned char* mask,
+                         const int32_t* forced, int32_t* ids, int32_t* unfinished, int32_t* state, int force_eos_step,
+                         const int32_t* force_eos_rows, const void* tok_emb, const float* pos_emb, int pos_rows, int emb_half, float* next_x, int B,
+                         int V, int d, int max_length, int begin_index, int eos, int pad, void* scratch, void* stream);
+/* step 0's input: x[b] = tok_emb[ids[b][cur_len[b] - 1]] + pos_emb[pos[b]]; ids [B][ids_ld], cur_len, pos: HOST arrays; tok_emb [V][d] float
+ * or half (emb_half), pos_emb [pos_rows][d].  scratch: wt_dbg_dec_embed_scratch_bytes(B, ids_ld) bytes. */
+size_t wt_dbg_dec_embed_scratch_bytes(int B, int ids_ld);
+int wt_dbg_dec_embed(const int32_t* ids, int ids_ld, const int32_t* cur_len, const int32_t* pos, const void* tok_emb, int V, const float* pos_emb,
+                     int pos_rows, int emb_half, float* x, int B, int d, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,10 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_gemm_x3_tile", "wt_dbg_layernorm_split", "wt_dbg_encoder_convs_scratch_bytes", "wt_dbg_encoder_convs", "wt_dbg_cross_kv",
                  "wt_dbg_timestamp_select_scratch_bytes", "wt_dbg_timestamp_select",
                  "wt_dbg_beam_select_scratch_bytes", "wt_dbg_beam_select", "wt_dbg_decode_attention_beam", "wt_dbg_decode_attention_rows", "wt_dbg_beam_trace",
-                 "wt_dbg_decode_attention_grouped", "wt_dbg_beam_logits"]
+                 "wt_dbg_decode_attention_grouped", "wt_dbg_beam_logits",
+                 "wt_dbg_vocab_argmax_parts", "wt_dbg_vocab_argmax_scratch_bytes", "wt_dbg_vocab_argmax", "wt_dbg_skinny_qkv_append_scratch_bytes",
+                 "wt_dbg_skinny_qkv_append", "wt_dbg_greedy_select_scratch_bytes", "wt_dbg_greedy_select", "wt_dbg_dec_embed_scratch_bytes",
+                 "wt_dbg_dec_embed"]
 
 
 class TensorDesc(Structure):
@@ -160,6 +163,19 @@ def load():
     lib.wt_dbg_beam_trace.argtypes = [c_void_p, P, I, P]
     lib.wt_dbg_decode_attention_grouped.argtypes = [P, P, P, P, P, P, I, I, I, I, I, I, I, P]
     lib.wt_dbg_beam_logits.argtypes = [c_void_p, P, P]
+    lib.wt_dbg_vocab_argmax_parts.argtypes = [I, I, I, I]
+    lib.wt_dbg_vocab_argmax_scratch_bytes.argtypes = []
+    lib.wt_dbg_vocab_argmax_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_vocab_argmax.argtypes = [P, P, P, P, P, P, POINTER(c_int32), I, I, I, I, I, I, I, I, P, P, P, P, P]
+    lib.wt_dbg_skinny_qkv_append_scratch_bytes.argtypes = []
+    lib.wt_dbg_skinny_qkv_append_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_skinny_qkv_append.argtypes = [P, P, P, P, P, P, P, P, POINTER(c_int32), I, I, I, I, I, I, F, P, P]
+    lib.wt_dbg_greedy_select_scratch_bytes.argtypes = [I]
+    lib.wt_dbg_greedy_select_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_greedy_select.argtypes = [P, P, P, I, P, POINTER(c_int32), P, P, POINTER(c_int32), I, POINTER(c_int32), P, P, I, I, P, I, I, I, I, I, I, I, P, P]
+    lib.wt_dbg_dec_embed_scratch_bytes.argtypes = [I, I]
+    lib.wt_dbg_dec_embed_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_dec_embed.argtypes = [POINTER(c_int32), I, POINTER(c_int32), POINTER(c_int32), P, I, P, I, I, P, I, I, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

@@ -435,3 +435,152 @@ extern "C" int wt_dbg_decode_attention_grouped(const float* q, const void* kcach
     a.n_split = n_split; a.fixed_len = len; a.nt = 1; a.kv_half = kv_half ? 1 : 0; a.group = group;
     return rc_of(launch_dec_attn(a, (hipStream_t)stream));
 }
+
+// ---- the greedy step's fused launches, parameterised by the engine's own helpers (wt_common.h): the vocabulary GEMV with the argmax
+// epilogue, the q|k|v projection with the in-place cache append, greedy_select_kernel + greedy_finish_kernel<false>, dec_embed_kernel ----
+static size_t dbg_align(size_t n) { return (n + 255) & ~(size_t)255; }
+// upload a host DecState to `dst`; synchronises (pageable source)
+static int upload_state(void* dst, const DecState& h, hipStream_t s) {
+    int rc = rc_of(hipMemcpyAsync(dst, &h, sizeof h, hipMemcpyHostToDevice, s));
+    return rc ? rc : rc_of(hipStreamSynchronize(s));
+}
+static SkinnyParams dbg_vocab_params(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* logits,
+                                     const DecState* st, int B, int N, int K, int xmode, int w_half, int w_nt) {
+    SkinnyParams k = vocab_skinny_params(X, ln_w, ln_b, W, logits, st, B, N, K, w_nt ? 1 : 0, w_half ? 1 : 0);
+    if (!xmode) k.xmode = XMODE_PLAIN;   // the engine always normalises and has no bias; the exact-integer cases need neither / both
+    k.bias = bias;
+    return k;
+}
+extern "C" int wt_dbg_vocab_argmax_parts(int B, int N, int K, int w_half) {
+    if (B < 1 || B > MAX_ROWS || N < 1 || K < 8 || K > 1024) return -1;
+    return skinny_grid(dbg_vocab_params(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, B, N, K, 1, w_half, 0));
+}
+extern "C" size_t wt_dbg_vocab_argmax_scratch_bytes(void) { return dbg_align(sizeof(DecState)); }
+extern "C" int wt_dbg_vocab_argmax(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, const unsigned char* mask,
+                                   const int32_t* cur_len, int begin_index, int B, int N, int K, int xmode, int w_half, int w_nt, int fused,
+                                   float* logits, float* part_val, int32_t* part_idx, void* scratch, void* stream) {
+    if (!X || !W || !cur_len || !scratch || B < 1 || B > MAX_ROWS || N < 1 || K < 8 || K > 1024 || (K & 7)) return -22;
+    if (xmode && (!ln_w || !ln_b)) return -22;
+    if (fused ? (!mask || !part_val || !part_idx) : !logits) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    DecState h;
+    memset(&h, 0, sizeof h);
+    for (int b = 0; b < B; ++b) h.cur_len[b] = cur_len[b];
+    int rc = upload_state(scratch, h, s);
+    if (rc) return rc;
+    SkinnyParams k = dbg_vocab_params(X, ln_w, ln_b, W, bias, fused ? nullptr : logits, (const DecState*)scratch, B, N, K, xmode, w_half, w_nt);
+    if (fused) {
+        SelectParams sp;
+        memset(&sp, 0, sizeof sp);
+        sp.mask = mask; sp.part_val = part_val; sp.part_idx = part_idx; sp.begin_index = begin_index; sp.trace = logits;
+        sp.max_length = 2;   // one trace row per batch row: [B][1][N], step 0
+        if (vocab_skinny_fuse_argmax(k, sp) < 1) return -22;
+    }
+    return rc_of(launch_skinny(k, s));
+}
+
+extern "C" size_t wt_dbg_skinny_qkv_append_scratch_bytes(void) { return dbg_align(sizeof(DecState)); }
+extern "C" int wt_dbg_skinny_qkv_append(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* q, void* kcache,
+                                        void* vcache, const int32_t* self_len, int B, int d, int s_cap, int w_half, int kv_half, int w_nt, float scale,
+                                        void* scratch, void* stream) {
+    if (!X || !ln_w || !ln_b || !W || !q || !kcache || !vcache || !self_len || !scratch) return -22;
+    if (B < 1 || B > MAX_ROWS || d < 64 || d > 1024 || (d & 63) || s_cap < 1) return -22;
+    for (int b = 0; b < B; ++b)
+        if (self_len[b] < 0 || self_len[b] >= s_cap) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    DecState h;
+    memset(&h, 0, sizeof h);
+    for (int b = 0; b < B; ++b) h.self_len[b] = self_len[b];
+    int rc = upload_state(scratch, h, s);
+    if (rc) return rc;
+    SkinnyParams k = qkv_append_skinny_params(X, ln_w, ln_b, W, bias, q, kcache, vcache, (const DecState*)scratch, B, d, s_cap, w_nt ? 1 : 0,
+                                              w_half ? 1 : 0, kv_half ? 1 : 0);
+    k.q_scale = scale;
+    return rc_of(launch_skinny(k, s));
+}
+
+static void dbg_state_to_dev(const int32_t* w, DecState& h) {
+    memset(&h, 0, sizeof h);
+    h.done = w[0]; h.n_unfinished = w[1]; h.step = w[2]; h.seq = w[3];
+    for (int b = 0; b < MAX_ROWS; ++b) {
+        h.cur_len[b] = w[4 + b]; h.pos[b] = w[4 + MAX_ROWS + b]; h.self_len[b] = w[4 + 2 * MAX_ROWS + b];
+        h.slot_row[b] = -1; h.row_force[b] = -1;
+    }
+}
+static void dbg_state_to_host(const DecState& h, int32_t* w) {
+    w[0] = h.done; w[1] = h.n_unfinished; w[2] = h.step; w[3] = h.seq;
+    for (int b = 0; b < MAX_ROWS; ++b) {
+        w[4 + b] = h.cur_len[b]; w[4 + MAX_ROWS + b] = h.pos[b]; w[4 + 2 * MAX_ROWS + b] = h.self_len[b];
+    }
+}
+struct SelScratch { size_t st, forced, rows, pv, pi, total; };
+static SelScratch sel_scratch_layout(int max_length) {
+    SelScratch l;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = dbg_align(off + bytes); return o; };
+    l.st = take(sizeof(DecState)); l.forced = take((size_t)(max_length + 1) * 4); l.rows = take(MAX_ROWS * 4);
+    l.pv = take((size_t)MAX_ROWS * SELECT_CHUNKS * 4); l.pi = take((size_t)MAX_ROWS * SELECT_CHUNKS * 4);
+    l.total = off;
+    return l;
+}
+extern "C" size_t wt_dbg_greedy_select_scratch_bytes(int max_length) { return max_length < 2 ? 0 : sel_scratch_layout(max_length).total; }
+extern "C" int wt_dbg_greedy_select(const float* logits, const float* part_val, const int32_t* part_idx, int n_parts, const unsigned char* mask,
+                                    const int32_t* forced, int32_t* ids, int32_t* unfinished, int32_t* state, int force_eos_step,
+                                    const int32_t* force_eos_rows, const void* tok_emb, const float* pos_emb, int pos_rows, int emb_half, float* next_x,
+                                    int B, int V, int d, int max_length, int begin_index, int eos, int pad, void* scratch, void* stream) {
+    const bool fused = logits == nullptr;
+    if (!mask || !forced || !ids || !unfinished || !state || !scratch || B < 1 || B > MAX_ROWS || V < 1 || max_length < 2) return -22;
+    if (fused ? (!part_val || !part_idx || n_parts < 1) : (part_val || part_idx)) return -22;
+    if (eos < 0 || eos >= V || pad < 0 || pad >= V) return -22;
+    if (next_x && (!tok_emb || !pos_emb || d < 4 || (d & 3))) return -22;
+    for (int b = 0; b < B; ++b)   // greedy_select_kernel reads cur_len[b]; greedy_finish_kernel indexes ids / forced / pos_emb by row 0's counters
+        if (state[4 + b] < 1 || state[4 + b] >= max_length) return -22;
+    if (next_x && (state[4 + MAX_ROWS] < -1 || state[4 + MAX_ROWS] + 1 >= pos_rows)) return -22;
+    for (int i = 0; i < max_length; ++i)
+        if (forced[i] >= V) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    const SelScratch l = sel_scratch_layout(max_length);
+    char* base = (char*)scratch;
+    DecState h;
+    dbg_state_to_dev(state, h);
+    int rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.forced, forced, (size_t)max_length * 4, hipMemcpyHostToDevice, s)))) return rc;
+    if (force_eos_rows && (rc = rc_of(hipMemcpyAsync(base + l.rows, force_eos_rows, (size_t)B * 4, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = upload_state(base + l.st, h, s))) return rc;
+    SelectParams p;
+    greedy_select_params(p, logits, mask, (const int*)(base + l.forced), ids, unfinished, (DecState*)(base + l.st), nullptr,
+                         fused ? const_cast<float*>(part_val) : (float*)(base + l.pv), fused ? const_cast<int32_t*>(part_idx) : (int*)(base + l.pi),
+                         tok_emb, pos_emb, next_x, d, emb_half ? 1 : 0, B, V, max_length, begin_index, eos, pad, force_eos_step,
+                         force_eos_rows ? (const int*)(base + l.rows) : nullptr, nullptr, 0);
+    if (fused) greedy_select_fused(p, n_parts);
+    if ((rc = rc_of(launch_greedy_select(p, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(&h, base + l.st, sizeof h, hipMemcpyDeviceToHost, s)))) return rc;
+    if ((rc = rc_of(hipStreamSynchronize(s)))) return rc;
+    dbg_state_to_host(h, state);
+    return 0;
+}
+
+extern "C" size_t wt_dbg_dec_embed_scratch_bytes(int B, int ids_ld) {
+    return B < 1 || ids_ld < 1 ? 0 : dbg_align(sizeof(DecState)) + dbg_align((size_t)B * ids_ld * 4);
+}
+extern "C" int wt_dbg_dec_embed(const int32_t* ids, int ids_ld, const int32_t* cur_len, const int32_t* pos, const void* tok_emb, int V,
+                                const float* pos_emb, int pos_rows, int emb_half, float* x, int B, int d, void* scratch, void* stream) {
+    if (!ids || !cur_len || !pos || !tok_emb || !pos_emb || !x || !scratch || B < 1 || B > MAX_ROWS || d < 4 || (d & 3) || ids_ld < 1) return -22;
+    for (int b = 0; b < B; ++b) {
+        if (cur_len[b] < 1 || cur_len[b] > ids_ld || pos[b] < 0 || pos[b] >= pos_rows) return -22;
+        const int tok = ids[(size_t)b * ids_ld + cur_len[b] - 1];
+        if (tok < 0 || tok >= V) return -22;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    char* base = (char*)scratch;
+    int* ids_dev = (int*)(base + dbg_align(sizeof(DecState)));
+    DecState h;
+    memset(&h, 0, sizeof h);
+    for (int b = 0; b < B; ++b) {
+        h.cur_len[b] = cur_len[b];
+        h.pos[b] = pos[b];
+    }
+    int rc = rc_of(hipMemcpyAsync(ids_dev, ids, (size_t)B * ids_ld * 4, hipMemcpyHostToDevice, s));
+    if (rc || (rc = upload_state(base, h, s))) return rc;
+    return rc_of(launch_dec_embed(ids_dev, ids_ld, (const float*)tok_emb, pos_emb, x, B, d, (const DecState*)base, s, emb_half ? 1 : 0));
+}

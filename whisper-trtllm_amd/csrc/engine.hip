@@ -760,9 +760,7 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
     memset(&a, 0, sizeof a);
     switch (part) {
     case LP_QKV:  // self attention (model.py:273-281, 283-304): LN -> q|k|v, append k/v row in place
-        k.X = h; k.ln_w = l.ln1_w; k.ln_b = l.ln1_b; k.xmode = XMODE_LAYERNORM; k.W = l.qkv_w; k.bias = l.qkv_b;
-        k.Y = e->dq; k.kcache = sk; k.vcache = sv; k.st = e->st; k.B = B; k.N = 3 * d; k.K = d; k.ymode = YMODE_QKV_APPEND;
-        k.d_model = d; k.s_cap = io.self_cap; k.q_scale = 0.125f; k.w_nt = e->nt_loads; k.w_half = wh; k.kv_half = kvh;
+        k = qkv_append_skinny_params(h, l.ln1_w, l.ln1_b, l.qkv_w, l.qkv_b, e->dq, sk, sv, e->st, B, d, io.self_cap, e->nt_loads, wh, kvh);
         LAUNCH(launch_skinny(k, s));
         break;
     case LP_SELF_ATTN:
@@ -836,16 +834,10 @@ static int enqueue_step(wt_engine* e, const StepIO& io, hipStream_t s) {
         std::swap(h, h1);
     }
     // final LN + vocabulary projection (model.py:455-457; logits are the engine's 'hidden_states' output)
-    memset(&k, 0, sizeof k);
-    k.X = h; k.ln_w = e->dec_ln_w; k.ln_b = e->dec_ln_b; k.xmode = XMODE_LAYERNORM; k.W = e->proj_w; k.Y = io.logits;
-    k.st = e->st; k.B = B; k.N = e->V; k.K = d; k.q_scale = 1.f; k.w_nt = e->nt_loads; k.w_half = e->w_half;
+    k = vocab_skinny_params(h, e->dec_ln_w, e->dec_ln_b, e->proj_w, io.logits, e->st, B, e->V, d, e->nt_loads, e->w_half);
     if (io.argmax) {  // Suppress -> SuppressAtBegin -> argmax in the epilogue (Force / pad / EOS rules: greedy_finish_kernel)
-        const SelectParams& sp = *io.argmax;
-        k.ymode = YMODE_ARGMAX; k.Y = nullptr; k.am_mask = sp.mask; k.am_val = sp.part_val; k.am_idx = sp.part_idx;
-        k.am_begin_index = sp.begin_index; k.am_trace = sp.trace; k.am_trace_steps = sp.max_length - 1;
-        const int grid = skinny_grid(k);
+        const int grid = vocab_skinny_fuse_argmax(k, *io.argmax);
         if (grid < 1 || grid > SEL_PARTS_CAP) return fail(WT_E_UNSUPPORTED, "vocabulary GEMV plan has %d workgroups (cap %d)", grid, SEL_PARTS_CAP);
-        k.am_ld = grid;
         *io.argmax_parts = grid;
     }
     {
@@ -1078,14 +1070,9 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
 static bool beam_on(const wt_engine* e) { return e->beam_cur.num_beams > 1 && !e->stream_mode; }
 
 static void fill_select_params(wt_engine* e, SelectParams& sp) {
-    memset(&sp, 0, sizeof sp);
-    sp.logits = e->logits; sp.mask = e->mask; sp.forced = e->forced; sp.ids = e->ids; sp.unfinished = e->unfinished;
-    sp.st = e->st; sp.trace = e->trace; sp.B = e->B; sp.V = e->V; sp.max_length = e->max_length;
-    sp.begin_index = e->begin_index; sp.eos = e->eos; sp.pad = e->pad; sp.force_eos_step = e->force_eos_step;
-    sp.part_val = e->sel_val; sp.part_idx = e->sel_idx; sp.tok_emb = e->tok_emb; sp.pos_emb = e->pos_emb; sp.next_x = e->dh;
-    sp.d_model = e->d; sp.n_parts = 8; sp.fused = 0; sp.emb_half = e->w_half;
-    sp.force_eos_rows = e->force_rows_on ? e->force_rows : nullptr; sp.mailbox = e->mailbox_dev;
-    sp.start_token = e->start_token;
+    greedy_select_params(sp, e->logits, e->mask, e->forced, e->ids, e->unfinished, e->st, e->trace, e->sel_val, e->sel_idx, e->tok_emb, e->pos_emb,
+                         e->dh, e->d, e->w_half, e->B, e->V, e->max_length, e->begin_index, e->eos, e->pad, e->force_eos_step,
+                         e->force_rows_on ? e->force_rows : nullptr, e->mailbox_dev, e->start_token);
     if (e->ts_cur.enabled && !e->stream_mode) {
         sp.ts_on = 1; sp.no_ts = e->ts_cur.no_timestamps_token_id; sp.tb = e->ts_cur.timestamp_begin;
         sp.ts_begin_index = e->ts_cur.begin_index; sp.max_init = e->ts_cur.max_initial_timestamp_index; sp.ts_part = e->ts_part;
@@ -1119,7 +1106,7 @@ static int enqueue_fast_step(wt_engine* e, hipStream_t s, int variant = 0) {
     io.argmax_parts = &parts;
     int rc = enqueue_step(e, io, s);
     if (rc) return rc;
-    if (fused) { sp.fused = 1; sp.n_parts = parts; }
+    if (fused) greedy_select_fused(sp, parts);
     LAUNCH(launch_greedy_select(sp, s));
     return WT_OK;
 }

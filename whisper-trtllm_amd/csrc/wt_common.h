@@ -323,6 +323,55 @@ hipError_t launch_copy_cache_rows(const float* src, float* dst, int LH, int src_
                                   hipStream_t s);
 hipError_t launch_set_state(DecState* st, int cur_len, int pos, int self_len, hipStream_t s);
 
+// ---- SkinnyParams / SelectParams of the greedy step's fused launches.  engine.hip and the debug hooks (debug_api.hip) both build their
+// launches here, so a test of a hook (tests/test_gpu_select.py) is a test of what the engine launches.
+// LayerNorm + fused q|k|v projection of one decoder layer: q (scaled by head_dim^-0.5) -> q [B][d], the k / v rows appended in place at
+// st->self_len[b] into the layer's self caches [B][H][s_cap][64] (float, or IEEE half with kv_half)
+inline SkinnyParams qkv_append_skinny_params(const float* h, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* q,
+                                             void* kcache, void* vcache, const DecState* st, int B, int d, int s_cap, int w_nt, int w_half,
+                                             int kv_half) {
+    SkinnyParams k;
+    memset(&k, 0, sizeof k);
+    k.X = h; k.ln_w = ln_w; k.ln_b = ln_b; k.xmode = XMODE_LAYERNORM; k.W = (const float*)W; k.bias = bias;
+    k.Y = q; k.kcache = (float*)kcache; k.vcache = (float*)vcache; k.st = st; k.B = B; k.N = 3 * d; k.K = d; k.ymode = YMODE_QKV_APPEND;
+    k.d_model = d; k.s_cap = s_cap; k.q_scale = 0.125f; k.w_nt = w_nt; k.w_half = w_half; k.kv_half = kv_half;
+    return k;
+}
+// final LayerNorm + vocabulary projection (no bias): plain logits [B][V] ...
+inline SkinnyParams vocab_skinny_params(const float* h, const float* ln_w, const float* ln_b, const void* W, float* logits, const DecState* st,
+                                        int B, int V, int d, int w_nt, int w_half) {
+    SkinnyParams k;
+    memset(&k, 0, sizeof k);
+    k.X = h; k.ln_w = ln_w; k.ln_b = ln_b; k.xmode = XMODE_LAYERNORM; k.W = (const float*)W; k.Y = logits;
+    k.st = st; k.B = B; k.N = V; k.K = d; k.q_scale = 1.f; k.w_nt = w_nt; k.w_half = w_half;
+    return k;
+}
+// ... or Suppress -> SuppressAtBegin -> argmax in the epilogue (Force / pad / EOS rules: greedy_finish_kernel): one partial per row and
+// workgroup into sp.part_val / part_idx [B][grid], the raw logits into sp.trace when set.  Returns the workgroup count (-1: no plan);
+// greedy_select_fused hands it to the finish kernel.
+inline int vocab_skinny_fuse_argmax(SkinnyParams& k, const SelectParams& sp) {
+    k.ymode = YMODE_ARGMAX; k.Y = nullptr; k.am_mask = sp.mask; k.am_val = sp.part_val; k.am_idx = sp.part_idx;
+    k.am_begin_index = sp.begin_index; k.am_trace = sp.trace; k.am_trace_steps = sp.max_length - 1;
+    const int grid = skinny_grid(k);
+    k.am_ld = grid;
+    return grid;
+}
+inline void greedy_select_fused(SelectParams& sp, int parts) { sp.fused = 1; sp.n_parts = parts; }
+// the plain greedy tail (greedy_select_kernel's SELECT_CHUNKS partials unless greedy_select_fused follows, then greedy_finish_kernel)
+inline void greedy_select_params(SelectParams& sp, const float* logits, const uint8_t* mask, const int* forced, int* ids, int* unfinished,
+                                 DecState* st, float* trace, float* part_val, int* part_idx, const void* tok_emb, const float* pos_emb,
+                                 float* next_x, int d, int emb_half, int B, int V, int max_length, int begin_index, int eos, int pad,
+                                 int force_eos_step, const int* force_eos_rows, unsigned long long* mailbox, int start_token) {
+    memset(&sp, 0, sizeof sp);
+    sp.logits = logits; sp.mask = mask; sp.forced = forced; sp.ids = ids; sp.unfinished = unfinished;
+    sp.st = st; sp.trace = trace; sp.B = B; sp.V = V; sp.max_length = max_length;
+    sp.begin_index = begin_index; sp.eos = eos; sp.pad = pad; sp.force_eos_step = force_eos_step;
+    sp.part_val = part_val; sp.part_idx = part_idx; sp.tok_emb = (const float*)tok_emb; sp.pos_emb = pos_emb; sp.next_x = next_x;
+    sp.d_model = d; sp.n_parts = SELECT_CHUNKS; sp.fused = 0; sp.emb_half = emb_half;
+    sp.force_eos_rows = force_eos_rows; sp.mailbox = mailbox;
+    sp.start_token = start_token;
+}
+
 // ---- GemmParams of the encoder's two convolutions and of the cross-K/V projection.  engine.hip and the debug hooks (debug_api.hip) both
 // build their launches here, so a test of a hook is a test of what the engine launches.
 // Conv workspace (per utterance b of B, Fr = 2 S frames): melT [B][Fr + 2][C] and c1 [B][Fr + 2][d], row t + 1 = frame t, rows 0 and
