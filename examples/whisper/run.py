@@ -51,6 +51,11 @@ def parse_arguments():
     parser.add_argument("--dump_ids", type=str, default=None, help="rank 0 writes the fast-path token ids as JSON (tests)")
     parser.add_argument("--return_timestamps", action="store_true", help="Whisper's timestamp mode: <|t|> tokens (t x 0.02 s) between "
                         "segments; printed as [start --> end] text segments with a tokenizer, as ids with <|t|> marks otherwise")
+    parser.add_argument("--return_token_timestamps", action="store_true", help="fast path: per-token times by cross-attention DTW on the "
+                        "device, printed as words with [start --> end] (with a tokenizer) or as ids with their times; needs a batch plan, no beams")
+    parser.add_argument("--alignment_heads", nargs="+", default=None, metavar="LAYER,HEAD", help="alignment heads for "
+                        "--return_token_timestamps, e.g. 2,1 3,0 (default: the checkpoint's generation_config.json; synthetic models have none)")
+    parser.add_argument("--median_filter_width", type=int, default=None, help="default: the config's median_filter_width, else 7")
     parser.add_argument("--num_beams", type=int, default=1, help="fast path: beam search on the device with this many beams (<= 8; batches are "
                         "sized so that utterances x beams <= 16 rows); needs a batch plan and no --return_timestamps")
     parser.add_argument("--length_penalty", type=float, default=1.0)
@@ -61,6 +66,15 @@ def parse_arguments():
     if args.num_beams > 1 and (args.batching == "continuous" or args.return_timestamps or args.session or args.compare):
         parser.error("--num_beams needs the fast path with a batch plan (--batching sorted | dataset): no --return_timestamps, --session or "
                      "--compare (the Session path decodes greedily)")
+    if args.return_token_timestamps and (args.batching == "continuous" or args.num_beams > 1 or args.session):
+        parser.error("--return_token_timestamps needs the fast path with a batch plan (--batching sorted | dataset) and no beams: the "
+                     "continuous mode keeps no query history, beam search no beam_indices, the Session path no cross attentions")
+    if args.alignment_heads is not None:
+        try:
+            args.alignment_heads = [tuple(int(x) for x in pair.split(",")) for pair in args.alignment_heads]
+            assert all(len(p) == 2 for p in args.alignment_heads)
+        except (ValueError, AssertionError):
+            parser.error("--alignment_heads takes LAYER,HEAD pairs, e.g. 2,1 3,0")
     if args.return_timestamps and args.batching == "continuous":
         parser.error("--return_timestamps needs a batch plan (--batching sorted | dataset): the continuous mode predicts no timestamps")
     return args
@@ -192,13 +206,23 @@ if __name__ == "__main__":
                 indexed = list(zip(range(begin, end), [r.tolist() for r in rows]))
             else:
                 kw = [{"return_timestamps": True}] * len(groups) if args.return_timestamps else None
+                if args.return_token_timestamps:
+                    one = {"return_token_timestamps": True, "alignment_heads": args.alignment_heads, "return_timestamps": args.return_timestamps,
+                           "median_filter_width": args.median_filter_width or int(config.get("median_filter_width", 7))}
+                    kw = [one] * len(groups)
                 if args.num_beams > 1:
                     kw = [{"num_beams": args.num_beams, "length_penalty": args.length_penalty, "early_stopping": args.early_stopping}] * len(groups)
                 for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):
-                    indexed += list(zip(g, ids.cpu().tolist()))
+                    if args.return_token_timestamps:     # (ids, seconds per token) of the batch
+                        indexed += list(zip(g, zip(ids[0].cpu().tolist(), ids[1].cpu().tolist())))
+                    else:
+                        indexed += list(zip(g, ids.cpu().tolist()))
             torch.cuda.synchronize()
             elapsed = tensorrt_llm.sharding.max_over_ranks(time.time() - t0, dist)
             ids = [row for _, row in sorted(tensorrt_llm.sharding.gather_objects(indexed, dist))]   # dataset order, on the host
+            if args.return_token_timestamps:
+                results["token_timestamps"] = [row[1] for row in ids]
+                ids = [row[0] for row in ids]
             results["fast"] = (elapsed, ids)
         if rank == 0:
             print(f"fast path   : {results['fast'][0]:.3f} s for {len(mels)} x 30 s on {world} rank(s)  ({30 * len(mels) / results['fast'][0]:.1f} audio-s/s)")
@@ -220,6 +244,7 @@ if __name__ == "__main__":
         b = [trim_after_eos(r, eos, pad) for r in results["session"][1]]
         diff = [(x, y) for x, y in zip(a, b) if x != y]
         print(f"Compare Result: same [{len(a) - len(diff)}], diff [{len(diff)}]")
+    token_times = results.pop("token_timestamps", None)
     if rank == 0:
         for key in results:
             print(key, "ids[0][:16] =", results[key][1][0][:16])
@@ -230,6 +255,15 @@ if __name__ == "__main__":
             if args.return_timestamps:
                 for seg in tok.offsets(ids):
                     print(f"  [{seg['timestamp'][0]:6.2f} --> {seg['timestamp'][1]:6.2f}] {seg['text']}")
+            if token_times is not None:
+                for w in tok.words(ids, token_times[args.audio.index(path)]):
+                    print(f"  [{w['timestamp'][0]:6.2f} --> {w['timestamp'][1]:6.2f}] {w['text']!r}")
+    elif rank == 0 and token_times is not None:      # no tokenizer: every token as its own word
+        eos, pad = config["eos_token_id"], config["pad_token_id"]
+        for i, (ids, ts) in enumerate(list(zip(results["fast"][1], token_times))[:4]):
+            n = len(trim_after_eos(ids, eos, pad))
+            ends = list(ts[1:]) + [ts[-1]]
+            print(f"utterance {i} token times:", " ".join(f"{t}[{a:.2f}-->{b:.2f}]" for t, a, b in zip(ids[:n], ts[:n], ends[:n])))
     elif rank == 0 and args.return_timestamps:       # no tokenizer: ids with the timestamps written out
         tb = tensorrt_llm.runtime.timestamp_rules(config)[1]
         for i, ids in enumerate(next(iter(results.values()))[1][:4]):

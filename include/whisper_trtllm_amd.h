@@ -213,6 +213,31 @@ typedef struct {
 int wt_decoder_set_beam_search(wt_engine* dec, const wt_beam_params* b);
 int wt_decoder_read_beam_scores(wt_engine* dec, float* scores_out, void* stream);
 
+/* (9d) token-level timestamps for the batch decode (wt_decoder_begin / _steps / _run / _greedy): transformers'
+ * WhisperForConditionalGeneration._extract_token_timestamps (cross-attention weights of the alignment heads -> normalisation over the
+ * tokens -> median filter along the frames -> mean over the heads -> dynamic time warping), on the device.  With the mode on, the
+ * cross-attention launches of the listed (layer, head) pairs also store their finished query per row and step (fp32, n_heads x rows x
+ * (max_length - 1) x 64 floats, allocated by wt_decoder_begin), and every row keeps stepping on pad input after its EOS, as the
+ * reference's rows do: those steps are part of the alignment.  wt_decoder_read_token_timestamps then runs the post-pass over that
+ * history and the resident cross-K cache, stream-ordered: with N = cur_len - 1 steps (the batch-wide length, for every row, as the
+ * reference) and S encoder frames, per utterance W = softmax(q K^T) per head [N][S] in fp32, (W - mean) / std over the tokens (population
+ * std; a single token gives NaN as in the reference), a median of `median_filter_width` along the frames with reflect padding (the input
+ * unchanged when S <= width / 2), the mean over the heads, DTW on the negated matrix (fp32 cost, ties resolved as
+ * _dynamic_time_warping does), and out[b][0] = 0, out[b][1 + k] = time_precision x the frame at which the path reaches token k; entries
+ * from cur_len on are 0.  `out` is DEVICE float [batch][ld], ld >= max_length; call it before the next wt_decoder_begin.
+ * The setting applies from the next wt_decoder_begin on this handle; t == NULL or n_heads <= 0 turns it off, and the engine then enqueues
+ * exactly what it did before.  WT_E_INVALID for a (layer, head) outside the model or listed twice, more than 32 heads, or a width that is
+ * not odd in [1, 15]; wt_decoder_begin refuses (WT_E_UNSUPPORTED) the mode together with beam search (it would need beam_indices), and
+ * wt_decoder_stream_begin refuses it.  It combines with the timestamp mode (9b) and with force_eos_step(s). */
+typedef struct {
+    int32_t n_heads;
+    const int32_t* heads;            /* host pointer, n_heads pairs (layer, head); copied by the call */
+    int32_t median_filter_width;     /* odd, 1 .. 15 (transformers' default: 7) */
+    double time_precision;           /* seconds per encoder frame (Whisper: 0.02) */
+} wt_token_timestamp_params;
+int wt_decoder_set_token_timestamps(wt_engine* dec, const wt_token_timestamp_params* t);
+int wt_decoder_read_token_timestamps(wt_engine* dec, float* out, int ld, void* stream);
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

@@ -192,6 +192,34 @@ size_t wt_dbg_dec_embed_scratch_bytes(int B, int ids_ld);
 int wt_dbg_dec_embed(const int32_t* ids, int ids_ld, const int32_t* cur_len, const int32_t* pos, const void* tok_emb, int V, const float* pos_emb,
                      int pos_rows, int emb_half, float* x, int B, int d, void* scratch, void* stream);
 
+/* ---- token-level timestamps (tests/test_gpu_token_timestamps.py): the post-pass launches, built by the engine's own parameter struct
+ * (wt_common.h TokTsParams).
+ * matrix: q_hist f32 [n_sel][N][64] and K [n_sel][S][64] (float, or IEEE half with kv_half) of ONE utterance -> W = softmax(q K^T) per head,
+ * normalised over the N tokens, median of `width` along S, mean over the heads -> matrix_out f32 [N][S].  `w_out` (or NULL) receives the
+ * softmax rows [n_sel][N][S] before the normalisation.
+ * median: w_in f32 [n_sel][N][S] taken as already normalised -> median of `width` + mean over the heads -> matrix_out [N][S] (with
+ * n_sel = 1 the median alone: a selection, so the output equals an input element bit for bit).
+ * dtw: matrix f32 [B][N][S] -> ts_out f32 [B][N + 1] (entry 0 = 0), path_out int32 [B][2][N + S] (text indices, then time indices, in
+ * backtrace order: last cell first), path_len int32 [B].
+ * scratch: wt_dbg_token_timestamps_scratch_bytes(n_sel, B, N, S) bytes. */
+size_t wt_dbg_token_timestamps_scratch_bytes(int n_sel, int B, int N, int S);
+int wt_dbg_token_timestamp_matrix_kernels(const float* q_hist, const void* K, int kv_half, int n_sel, int N, int S, int width, float* w_out,
+                                          float* matrix_out, void* scratch, void* stream);
+int wt_dbg_token_timestamp_median(const float* w_in, int n_sel, int N, int S, int width, float* matrix_out, void* scratch, void* stream);
+int wt_dbg_token_timestamp_dtw(const float* matrix, int B, int N, int S, double time_precision, float* ts_out, int32_t* path_out,
+                               int32_t* path_len, void* scratch, void* stream);
+/* a decode with token-level timestamps in flight: the captured queries, device f32 [n_sel][rows][max_length - 1][64] (steps not yet
+ * executed are 0), and -- after wt_decoder_read_token_timestamps -- the matrix, device f32 [rows][max_length - 1][S] (token rows from
+ * cur_len - 1 on are not written) */
+int wt_dbg_token_timestamp_q_hist(wt_engine* dec, float* out, void* stream);
+int wt_dbg_token_timestamp_matrix(wt_engine* dec, float* out, void* stream);
+/* the halves of the post-pass alone (timing): which = 1 the matrix launches of every utterance, 2 the DTW launch over the matrix as it
+ * stands; and the bytes of the mode's device allocation (query history, head table, W, statistics, matrix, trace, output) */
+int wt_dbg_token_timestamp_postpass(wt_engine* dec, int which, void* stream);
+size_t wt_dbg_token_timestamp_bytes(const wt_engine* dec);
+/* the resident cross-K rows of one (layer, head) of the decode in flight, widened to float: HOST f32 [rows][S][64].  Synchronises. */
+int wt_dbg_cross_k_head(wt_engine* dec, int layer, int head, float* out_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

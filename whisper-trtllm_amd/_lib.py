@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libwhisper_trtllm_amd.so")
@@ -17,7 +17,8 @@ ABI_VERSION = 3
 EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
-    "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores",
+    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
     "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_last_error", "wt_abi_version",
 ]
@@ -30,7 +31,10 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_decode_attention_grouped", "wt_dbg_beam_logits",
                  "wt_dbg_vocab_argmax_parts", "wt_dbg_vocab_argmax_scratch_bytes", "wt_dbg_vocab_argmax", "wt_dbg_skinny_qkv_append_scratch_bytes",
                  "wt_dbg_skinny_qkv_append", "wt_dbg_greedy_select_scratch_bytes", "wt_dbg_greedy_select", "wt_dbg_dec_embed_scratch_bytes",
-                 "wt_dbg_dec_embed"]
+                 "wt_dbg_dec_embed",
+                 "wt_dbg_token_timestamps_scratch_bytes", "wt_dbg_token_timestamp_matrix_kernels", "wt_dbg_token_timestamp_median",
+                 "wt_dbg_token_timestamp_dtw", "wt_dbg_token_timestamp_q_hist", "wt_dbg_token_timestamp_matrix", "wt_dbg_cross_k_head",
+                 "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes"]
 
 
 class TensorDesc(Structure):
@@ -61,6 +65,10 @@ class TimestampParams(Structure):
 
 class BeamParams(Structure):
     _fields_ = [("num_beams", c_int32), ("length_penalty", c_float), ("early_stopping", c_int32)]
+
+
+class TokenTimestampParams(Structure):
+    _fields_ = [("n_heads", c_int32), ("heads", POINTER(c_int32)), ("median_filter_width", c_int32), ("time_precision", c_double)]
 
 
 class KernelTimer(Structure):
@@ -111,6 +119,8 @@ def load():
     lib.wt_decoder_set_timestamp_rules.argtypes = [c_void_p, POINTER(TimestampParams)]
     lib.wt_decoder_set_beam_search.argtypes = [c_void_p, POINTER(BeamParams)]
     lib.wt_decoder_read_beam_scores.argtypes = [c_void_p, c_void_p, c_void_p]
+    lib.wt_decoder_set_token_timestamps.argtypes = [c_void_p, POINTER(TokenTimestampParams)]
+    lib.wt_decoder_read_token_timestamps.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -176,6 +186,17 @@ def load():
     lib.wt_dbg_dec_embed_scratch_bytes.argtypes = [I, I]
     lib.wt_dbg_dec_embed_scratch_bytes.restype = c_size_t
     lib.wt_dbg_dec_embed.argtypes = [POINTER(c_int32), I, POINTER(c_int32), POINTER(c_int32), P, I, P, I, I, P, I, I, P, P]
+    lib.wt_dbg_token_timestamps_scratch_bytes.argtypes = [I, I, I, I]
+    lib.wt_dbg_token_timestamps_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_token_timestamp_matrix_kernels.argtypes = [P, P, I, I, I, I, I, P, P, P, P]
+    lib.wt_dbg_token_timestamp_median.argtypes = [P, I, I, I, I, P, P, P]
+    lib.wt_dbg_token_timestamp_dtw.argtypes = [P, I, I, I, c_double, P, P, P, P, P]
+    lib.wt_dbg_token_timestamp_q_hist.argtypes = [c_void_p, P, P]
+    lib.wt_dbg_token_timestamp_matrix.argtypes = [c_void_p, P, P]
+    lib.wt_dbg_cross_k_head.argtypes = [c_void_p, I, I, P, P]
+    lib.wt_dbg_token_timestamp_postpass.argtypes = [c_void_p, I, P]
+    lib.wt_dbg_token_timestamp_bytes.argtypes = [c_void_p]
+    lib.wt_dbg_token_timestamp_bytes.restype = c_size_t
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

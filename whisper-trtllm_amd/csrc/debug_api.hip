@@ -584,3 +584,62 @@ extern "C" int wt_dbg_dec_embed(const int32_t* ids, int ids_ld, const int32_t* c
     if (rc || (rc = upload_state(base, h, s))) return rc;
     return rc_of(launch_dec_embed(ids_dev, ids_ld, (const float*)tok_emb, pos_emb, x, B, d, (const DecState*)base, s, emb_half ? 1 : 0));
 }
+
+// ---- token-level timestamps: the post-pass launches on caller-supplied inputs, through the engine's TokTsParams ----
+struct TtScratch { size_t W, mean, sdev, matrix, trace, total; };
+static TtScratch tt_scratch_layout(int n_sel, int B, int N, int S) {
+    TtScratch l;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
+    l.W = take((size_t)n_sel * N * S * 4); l.mean = take((size_t)n_sel * S * 4); l.sdev = take((size_t)n_sel * S * 4);
+    l.matrix = take((size_t)B * N * S * 4); l.trace = take((size_t)B * N * tt_trace_ld(S));
+    l.total = off;
+    return l;
+}
+static bool tt_dims_ok(int n_sel, int B, int N, int S) {
+    return n_sel >= 1 && n_sel <= TT_MAX_HEADS && B >= 1 && B <= MAX_ROWS && N >= 1 && N <= TT_MAX_TOKENS && S >= 1 && S <= 4000;
+}
+extern "C" size_t wt_dbg_token_timestamps_scratch_bytes(int n_sel, int B, int N, int S) {
+    return tt_dims_ok(n_sel, B, N, S) ? tt_scratch_layout(n_sel, B, N, S).total : 0;
+}
+static void tt_dbg_params(TokTsParams& p, int n_sel, int B, int N, int S, int width, void* scratch) {
+    const TtScratch l = tt_scratch_layout(n_sel, B, N, S);
+    char* base = (char*)scratch;
+    memset(&p, 0, sizeof p);
+    p.qh_rows = 1; p.qh_steps = N; p.cross_rows = 1; p.H = n_sel; p.S = S; p.n_sel = n_sel;
+    for (int i = 0; i < n_sel; ++i) { p.layer[i] = 0; p.head[i] = i; }
+    p.width = width; p.time_precision = 0.02; p.n_fixed = N; p.n_cap = N; p.B = B;
+    p.W = (float*)(base + l.W); p.mean = (float*)(base + l.mean); p.sdev = (float*)(base + l.sdev); p.matrix = (float*)(base + l.matrix);
+    p.trace = (uint8_t*)(base + l.trace); p.trace_ld = tt_trace_ld(S);
+}
+extern "C" int wt_dbg_token_timestamp_matrix_kernels(const float* q_hist, const void* K, int kv_half, int n_sel, int N, int S, int width, float* w_out,
+                                                     float* matrix_out, void* scratch, void* stream) {
+    if (!q_hist || !K || !matrix_out || !scratch || !tt_dims_ok(n_sel, 1, N, S) || width < 1 || width > TT_MAX_WIDTH || !(width & 1)) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    TokTsParams p;
+    tt_dbg_params(p, n_sel, 1, N, S, width, scratch);
+    p.q_hist = q_hist; p.cross_k = K; p.kv_half = kv_half ? 1 : 0;
+    int rc = rc_of(launch_tt_matrix(p, 0, s));
+    if (rc) return rc;
+    if (w_out && (rc = rc_of(hipMemcpyAsync(w_out, p.W, (size_t)n_sel * N * S * 4, hipMemcpyDeviceToDevice, s)))) return rc;
+    return rc_of(hipMemcpyAsync(matrix_out, p.matrix, (size_t)N * S * 4, hipMemcpyDeviceToDevice, s));
+}
+extern "C" int wt_dbg_token_timestamp_median(const float* w_in, int n_sel, int N, int S, int width, float* matrix_out, void* scratch, void* stream) {
+    if (!w_in || !matrix_out || !scratch || !tt_dims_ok(n_sel, 1, N, S) || width < 1 || width > TT_MAX_WIDTH || !(width & 1)) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    TokTsParams p;
+    tt_dbg_params(p, n_sel, 1, N, S, width, scratch);
+    p.W = const_cast<float*>(w_in); p.mean = nullptr; p.sdev = nullptr;
+    const int rc = rc_of(launch_tt_median(p, 0, s));
+    if (rc) return rc;
+    return rc_of(hipMemcpyAsync(matrix_out, p.matrix, (size_t)N * S * 4, hipMemcpyDeviceToDevice, s));
+}
+extern "C" int wt_dbg_token_timestamp_dtw(const float* matrix, int B, int N, int S, double time_precision, float* ts_out, int32_t* path_out,
+                                          int32_t* path_len, void* scratch, void* stream) {
+    if (!matrix || !ts_out || !path_out || !path_len || !scratch || !tt_dims_ok(1, B, N, S) || !(time_precision > 0.0)) return -22;
+    TokTsParams p;
+    tt_dbg_params(p, 1, B, N, S, 1, scratch);
+    p.matrix = const_cast<float*>(matrix); p.time_precision = time_precision;
+    p.path = path_out; p.path_len = path_len; p.out = ts_out; p.out_ld = N + 1;
+    return rc_of(launch_tt_dtw(p, (hipStream_t)stream));
+}

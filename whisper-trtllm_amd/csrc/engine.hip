@@ -152,6 +152,24 @@ struct wt_engine {
     int beam_U = 0;
     int beam_group = 0;           // > 1: the cross-attention of the beam decode in flight runs the grouped form (num_beams 2 or 4)
     BeamParams beam_dev = {};     // device buffers of the beam state (dec_reserve; nb / U / penalty filled per decode)
+    // token-level timestamps (wt_decoder_set_token_timestamps): the setting asked for (applied by the next wt_decoder_begin) and that of the
+    // decode in flight (n_sel == 0: off); the query history the cross-attention launches fill, and the post-pass workspace
+    struct TokTs {
+        int n_sel = 0, width = 7;
+        double time_precision = 0.02;
+        int layer[TT_MAX_HEADS] = {}, head[TT_MAX_HEADS] = {};
+        bool operator==(const TokTs& o) const {
+            return n_sel == o.n_sel && width == o.width && time_precision == o.time_precision &&
+                   memcmp(layer, o.layer, sizeof layer) == 0 && memcmp(head, o.head, sizeof head) == 0;
+        }
+    } tt_req, tt_cur;
+    char* tt_buf = nullptr;       // one allocation: q_hist, the per-layer head tables, W, statistics, matrix, trace, output
+    size_t tt_bytes = 0;
+    float *tt_qh = nullptr, *tt_W = nullptr, *tt_mean = nullptr, *tt_sdev = nullptr, *tt_matrix = nullptr, *tt_out = nullptr;
+    int* tt_sel = nullptr;        // device [L][H]: selection index of (layer, head), or -1
+    uint8_t* tt_trace = nullptr;
+    int tt_rows = 0, tt_steps = 0;   // q_hist / matrix dimensions of the decode in flight: rows = B, steps = max_length - 1
+    std::vector<int> tt_h_sel;    // host image of tt_sel
     hipStream_t own_stream = nullptr;
     // step graphs: [0] every row attends (the only one a decode without early finishers ever replays), [1] finished rows stream no K/V,
     // [2] / [3] the same two for the continuous mode (per-slot cross-cache rows, stream_finish_kernel)
@@ -229,6 +247,7 @@ extern "C" void wt_engine_close(wt_engine* e) {
     if (e->h_len) hipHostFree(e->h_len);
     if (e->enc_ws) hipFree(e->enc_ws);
     if (e->dec_ws) hipFree(e->dec_ws);
+    if (e->tt_buf) hipFree(e->tt_buf);
     e->weights.reset();   // the last handle sharing the payload frees it
     delete e;
 }
@@ -729,6 +748,9 @@ struct StepIO {
     int group = 0;                         // beam search: grouped cross attention (DecAttnParams.group) instead of slot_row
     const int* anc = nullptr;              // beam search: ancestry table of the self-attention (DecAttnParams.anc), row stride anc_ld
     int anc_ld = 0;
+    float* qh = nullptr;                   // token-level timestamps: query history of the cross attention (DecAttnParams.qh), [n_sel][qh_rows][qh_steps][64]
+    const int* qh_sel = nullptr;           // [L][H] selection index or -1
+    int qh_rows = 0, qh_steps = 0;
     int kv_esz;                            // bytes per cache element: 4 (fp32; always on the Session path), 2 (resident caches of an fp16 engine)
     float* logits;                         // [B][V]
     int B, nsplit_self, nsplit_cross;
@@ -789,6 +811,7 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
         a.n_split = io.nsplit_cross; a.fixed_len = e->S; a.nt = e->nt_loads; a.ln_h = h1; a.ln_r = l.fold_r; a.ln_t = l.fold_t; a.kv_half = kvh;
         a.alive = io.alive; a.slot_row = io.slot_row;
         if (io.group > 1) { a.group = io.group; a.slot_row = nullptr; }
+        if (io.qh) { a.qh = io.qh; a.qh_sel = io.qh_sel + (size_t)i * H; a.qh_rows = io.qh_rows; a.qh_steps = io.qh_steps; }
         a.defer_merge = defer && io.nsplit_cross == 2;  // the out-projection below merges the two split partials while staging them
                                                         // (more splits, i.e. batch < 8: the attention kernel merges its own, by ticket)
         hipEvent_t ta, tb;
@@ -891,6 +914,46 @@ static int cross_kv_project(wt_engine* e, const float* enc_hidden, int B, int ro
     return WT_OK;
 }
 
+// token-level timestamps: (re)allocate the query history and the post-pass workspace for `B` rows of `max_length - 1` steps and upload the
+// per-layer head tables.  The buffer only grows; its layout is recomputed per decode.
+static int tt_reserve(wt_engine* e, const wt_engine::TokTs& tt, int B, int max_length, hipStream_t s) {
+    const int n = tt.n_sel, steps = max_length - 1, S = e->S, ld = tt_trace_ld(S);
+    if (steps > TT_MAX_TOKENS) return fail(WT_E_UNSUPPORTED, "token timestamps: %d steps > %d", steps, TT_MAX_TOKENS);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    // the head table comes first: its address does not depend on the decode's dimensions
+    const size_t o_sel = take((size_t)e->L * e->H * 4), o_qh = take((size_t)n * B * steps * HEAD_DIM * 4), o_W = take((size_t)n * steps * S * 4);
+    const size_t o_mean = take((size_t)n * S * 4), o_sdev = take((size_t)n * S * 4), o_mat = take((size_t)B * steps * S * 4);
+    const size_t o_tr = take((size_t)B * steps * ld), o_out = take((size_t)B * max_length * 4);
+    if (off > e->tt_bytes) {
+        HIPCHK(hipStreamSynchronize(s));   // nothing of an earlier decode may still use the old buffer
+        if (e->tt_buf) { hipFree(e->tt_buf); e->tt_buf = nullptr; e->tt_bytes = 0; }
+        hipError_t he = hipMalloc((void**)&e->tt_buf, off);
+        if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for the token-timestamp workspace failed: %s", off, hipGetErrorString(he));
+        e->tt_bytes = off;
+        e->graph_valid = false;
+        e->tt_h_sel.clear();
+    }
+    char* b = e->tt_buf;
+    float* qh = (float*)(b + o_qh);
+    int* sel = (int*)(b + o_sel);
+    if (qh != e->tt_qh || sel != e->tt_sel || e->tt_rows != B || e->tt_steps != steps) e->graph_valid = false;
+    if (sel != e->tt_sel) e->tt_h_sel.clear();   // the table moved: whatever lies there is not the table, upload it again
+    e->tt_qh = qh; e->tt_sel = sel; e->tt_W = (float*)(b + o_W); e->tt_mean = (float*)(b + o_mean); e->tt_sdev = (float*)(b + o_sdev);
+    e->tt_matrix = (float*)(b + o_mat); e->tt_trace = (uint8_t*)(b + o_tr); e->tt_out = (float*)(b + o_out);
+    e->tt_rows = B; e->tt_steps = steps;
+    std::vector<int> tab((size_t)e->L * e->H, -1);
+    for (int i = 0; i < n; ++i) tab[(size_t)tt.layer[i] * e->H + tt.head[i]] = i;
+    if (tab != e->tt_h_sel) {
+        e->tt_h_sel.swap(tab);
+        HIPCHK(hipMemcpyAsync(e->tt_sel, e->tt_h_sel.data(), e->tt_h_sel.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));   // pageable source
+    }
+    // a row that is never stepped (a decode read before its first step) must not hand stale queries to the post-pass
+    HIPCHK(hipMemsetAsync(e->tt_qh, 0, (size_t)n * B * steps * HEAD_DIM * 4, s));
+    return WT_OK;
+}
+
 // Everything wt_decoder_begin and wt_decoder_stream_begin share: argument checks, workspace, token-rule tables, cache policy and key
 // splits of the step graph.  `B` = rows of the batch / decode slots of the stream; `pool_rows` = cross-cache rows (0: B).
 static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool_rows, bool stream_mode, hipStream_t s, const char* who,
@@ -947,6 +1010,14 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
         if (on != e->force_rows_on) e->graph_valid = false;
         e->force_rows_on = on;
     }
+    // token-level timestamps: workspace and head tables of this decode (a changed setting re-captures the step graphs)
+    const wt_engine::TokTs tt = stream_mode || beam.num_beams > 1 ? wt_engine::TokTs{} : e->tt_req;
+    if (tt.n_sel > 0) {
+        rc = tt_reserve(e, tt, B, p->max_length, s);
+        if (rc) return rc;
+    }
+    if (!(tt == e->tt_cur)) e->graph_valid = false;
+    e->tt_cur = tt;
     const bool same = e->begun && e->B == B && e->max_length == p->max_length && e->trace == p->logits_trace &&
                       e->begin_index == p->begin_index && e->eos == p->eos_token_id && e->pad == p->pad_token_id &&
                       e->force_eos_step == p->force_eos_step && e->start_token == p->decoder_start_token_id &&
@@ -1032,6 +1103,32 @@ extern "C" int wt_decoder_set_beam_search(wt_engine* e, const wt_beam_params* b)
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_token_timestamps(wt_engine* e, const wt_token_timestamp_params* t) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: not a decoder engine");
+    if (!t || t->n_heads <= 0) {
+        e->tt_req = wt_engine::TokTs{};
+        return WT_OK;
+    }
+    if (t->n_heads > TT_MAX_HEADS) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: %d alignment heads > %d", t->n_heads, TT_MAX_HEADS);
+    if (!t->heads) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: null head list");
+    if (t->median_filter_width < 1 || t->median_filter_width > TT_MAX_WIDTH || !(t->median_filter_width & 1))
+        return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: median_filter_width %d (odd, 1 .. %d)", t->median_filter_width, TT_MAX_WIDTH);
+    if (!(t->time_precision > 0.0) || !(t->time_precision < 1e6))
+        return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: time_precision %g", t->time_precision);
+    wt_engine::TokTs tt;
+    tt.n_sel = t->n_heads; tt.width = t->median_filter_width; tt.time_precision = t->time_precision;
+    for (int i = 0; i < t->n_heads; ++i) {
+        const int l = t->heads[2 * i], h = t->heads[2 * i + 1];
+        if (l < 0 || l >= e->L || h < 0 || h >= e->H)
+            return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: alignment head (%d, %d) outside %d layers x %d heads", l, h, e->L, e->H);
+        for (int j = 0; j < i; ++j)
+            if (tt.layer[j] == l && tt.head[j] == h) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: alignment head (%d, %d) listed twice", l, h);
+        tt.layer[i] = l; tt.head[i] = h;
+    }
+    e->tt_req = tt;
+    return WT_OK;
+}
+
 static void fill_select_params(wt_engine* e, SelectParams& sp);
 
 extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, const wt_greedy_params* p, void* stream) {
@@ -1042,6 +1139,8 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
     const int nb = beam.num_beams > 1 ? beam.num_beams : 1, U = B;
     if (nb > 1) {
         if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and timestamp mode cannot be combined");
+        if (e->tt_req.n_sel > 0)
+            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token-level timestamps cannot be combined (no beam_indices)");
         if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
             return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: logits_trace / force_eos_step(s) are not available with beam search");
         if (U * nb > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", U, nb, MAX_ROWS);
@@ -1068,6 +1167,7 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
 }
 
 static bool beam_on(const wt_engine* e) { return e->beam_cur.num_beams > 1 && !e->stream_mode; }
+static bool tt_on(const wt_engine* e) { return e->tt_cur.n_sel > 0 && !e->stream_mode; }
 
 static void fill_select_params(wt_engine* e, SelectParams& sp) {
     greedy_select_params(sp, e->logits, e->mask, e->forced, e->ids, e->unfinished, e->st, e->trace, e->sel_val, e->sel_idx, e->tok_emb, e->pos_emb,
@@ -1095,6 +1195,7 @@ static int enqueue_fast_step(wt_engine* e, hipStream_t s, int variant = 0) {
     io.cross_k = e->cross_k; io.cross_v = e->cross_v; io.cross_rows = e->cross_rows; io.logits = e->logits; io.B = e->B; io.kv_esz = e->kv_esz;
     io.slot_row = (variant & 2) ? e->st->slot_row : nullptr;   // (address arithmetic on a device pointer: nothing is dereferenced here)
     if (beam_on(e)) { io.slot_row = e->beam_dev.urow; io.anc = e->beam_dev.anc; io.anc_ld = e->beam_dev.anc_ld; io.group = e->beam_group; }
+    if (tt_on(e)) { io.qh = e->tt_qh; io.qh_sel = e->tt_sel; io.qh_rows = e->tt_rows; io.qh_steps = e->tt_steps; }
     io.nsplit_self = e->nsplit_self; io.nsplit_cross = e->nsplit_cross;
     io.embed = false;  // dh already holds this step's input: written by wt_decoder_begin (step 0) or by the previous greedy_finish
     static const bool fuse = tuning_env("WT_NO_FUSED_ARGMAX") == nullptr;  // A/B switch: logits to HBM + greedy_select_kernel
@@ -1122,6 +1223,7 @@ static std::mutex g_capture_mutex;
 // row's logits at every step as the reference computes them).  The continuous mode replays variants 2 / 3.
 static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant = 0) {
     if (e->trace || beam_on(e)) variant = 0;   // (beam search: one graph; a finished utterance's rows keep attending)
+    if (tt_on(e)) variant = 0;   // token-level timestamps: finished rows keep stepping on pad input, their steps are part of the alignment
     if (e->stream_mode) variant |= 2;
     if (e->profiling || !e->use_graph) {  // eager: per-kernel event timers need real launches
         for (int i = 0; i < n_steps; ++i) {
@@ -1181,6 +1283,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     if (pool_rows < slots + 1 || pool_rows > STREAM_QCAP) return fail(WT_E_INVALID, "wt_decoder_stream_begin: pool of %d rows outside [slots + 1, %d]", pool_rows, STREAM_QCAP);
     if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: timestamp mode is a batch-decode feature (wt_decoder_begin)");
     if (e->beam_req.num_beams > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: beam search is a batch-decode feature (wt_decoder_begin)");
+    if (e->tt_req.n_sel > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token-level timestamps are a batch-decode feature (wt_decoder_begin)");
     if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);
@@ -1449,6 +1552,85 @@ extern "C" int wt_decoder_read_beam_scores(wt_engine* e, float* scores_out, void
     fill_select_params(e, sp);
     LAUNCH(launch_beam_finalize(sp, (hipStream_t)stream));
     HIPCHK(hipMemcpyAsync(scores_out, e->beam_dev.out_scores, (size_t)e->beam_U * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+
+// the post-pass of the token-level timestamps over the decode in flight: q_hist x resident cross-K -> matrix -> DTW -> seconds
+static void tt_fill(const wt_engine* e, TokTsParams& p) {
+    memset(&p, 0, sizeof p);
+    const wt_engine::TokTs& tt = e->tt_cur;
+    p.q_hist = e->tt_qh; p.qh_rows = e->tt_rows; p.qh_steps = e->tt_steps;
+    p.cross_k = e->cross_k; p.kv_half = e->kv_esz == 2 ? 1 : 0; p.cross_rows = e->cross_rows; p.H = e->H; p.S = e->S;
+    p.n_sel = tt.n_sel;
+    memcpy(p.layer, tt.layer, sizeof p.layer);
+    memcpy(p.head, tt.head, sizeof p.head);
+    p.width = tt.width; p.time_precision = tt.time_precision;
+    p.st = e->st; p.n_cap = e->tt_steps; p.B = e->B;
+    p.W = e->tt_W; p.mean = e->tt_mean; p.sdev = e->tt_sdev; p.matrix = e->tt_matrix; p.trace = e->tt_trace; p.trace_ld = tt_trace_ld(e->S);
+    p.out = e->tt_out; p.out_ld = e->max_length;
+}
+extern "C" int wt_decoder_read_token_timestamps(wt_engine* e, float* out, int ld, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e))
+        return fail(WT_E_STATE, "wt_decoder_read_token_timestamps: no decode with token-level timestamps in flight");
+    if (!out || ld < e->max_length) return fail(WT_E_INVALID, "wt_decoder_read_token_timestamps: row stride %d < max_length %d", ld, e->max_length);
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    hipStream_t s = (hipStream_t)stream;
+    TokTsParams p;
+    tt_fill(e, p);
+    for (int b = 0; b < e->B; ++b) LAUNCH(launch_tt_matrix(p, b, s));
+    LAUNCH(launch_tt_dtw(p, s));
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)ld * 4, e->tt_out, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->B, hipMemcpyDeviceToDevice, s));
+    return WT_OK;
+}
+// the two halves of the post-pass alone, for timing (tools/token_timestamp_cost.py): which = 1 the matrix launches of every utterance,
+// 2 the DTW launch (over the matrix as it stands); and the bytes of the mode's device allocation
+extern "C" int wt_dbg_token_timestamp_postpass(wt_engine* e, int which, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e)) return fail(WT_E_STATE, "wt_dbg_token_timestamp_postpass: mode off");
+    if (which != 1 && which != 2) return fail(WT_E_INVALID, "wt_dbg_token_timestamp_postpass: which = %d", which);
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    hipStream_t s = (hipStream_t)stream;
+    TokTsParams p;
+    tt_fill(e, p);
+    if (which == 1) for (int b = 0; b < e->B; ++b) LAUNCH(launch_tt_matrix(p, b, s));
+    else LAUNCH(launch_tt_dtw(p, s));
+    return WT_OK;
+}
+extern "C" size_t wt_dbg_token_timestamp_bytes(const wt_engine* e) { return e ? e->tt_bytes : 0; }
+// debug read-backs (whisper_trtllm_amd_debug.h): the captured queries [n_sel][B][max_length - 1][64] and, after
+// wt_decoder_read_token_timestamps, the matrix [B][max_length - 1][S] (rows >= cur_len - 1 are not written)
+extern "C" int wt_dbg_token_timestamp_q_hist(wt_engine* e, float* out, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e)) return fail(WT_E_STATE, "wt_dbg_token_timestamp_q_hist: mode off");
+    if (!out) return fail(WT_E_INVALID, "wt_dbg_token_timestamp_q_hist: null output");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    HIPCHK(hipMemcpyAsync(out, e->tt_qh, (size_t)e->tt_cur.n_sel * e->tt_rows * e->tt_steps * HEAD_DIM * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+extern "C" int wt_dbg_token_timestamp_matrix(wt_engine* e, float* out, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e)) return fail(WT_E_STATE, "wt_dbg_token_timestamp_matrix: mode off");
+    if (!out) return fail(WT_E_INVALID, "wt_dbg_token_timestamp_matrix: null output");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    HIPCHK(hipMemcpyAsync(out, e->tt_matrix, (size_t)e->tt_rows * e->tt_steps * e->S * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+// the resident cross-K rows of one (layer, head): [B][S][64] widened to float (fp16 engines keep them in half) -- host staging, synchronises
+extern "C" int wt_dbg_cross_k_head(wt_engine* e, int layer, int head, float* out_host, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun) return fail(WT_E_STATE, "wt_dbg_cross_k_head: no decode in flight");
+    if (!out_host || layer < 0 || layer >= e->L || head < 0 || head >= e->H) return fail(WT_E_INVALID, "wt_dbg_cross_k_head: bad arguments");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    const size_t n = (size_t)e->S * HEAD_DIM;
+    std::vector<char> tmp(n * e->kv_esz);
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    for (int b = 0; b < e->B; ++b) {
+        const char* src = (const char*)e->cross_k + ((((size_t)layer * e->cross_rows + b) * e->H + head) * n) * e->kv_esz;
+        HIPCHK(hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost));
+        if (e->kv_esz == 4) memcpy(out_host + b * n, tmp.data(), n * 4);
+        else for (size_t i = 0; i < n; ++i) out_host[b * n + i] = (float)((const _Float16*)tmp.data())[i];
+    }
     return WT_OK;
 }
 

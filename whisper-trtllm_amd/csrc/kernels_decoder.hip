@@ -672,7 +672,11 @@ __device__ __forceinline__ float row8_allreduce_sum(float v) {   // sum over eac
 // G > 1 (beam search, cross attention, grouped form): the G beams of an utterance share its K/V, so ONE block streams cache row
 // blockIdx.z and carries the G query rows blockIdx.z * G + g against every key tile -- the keys are in registers already; it is G dot
 // products and online-softmax states per key instead of one, and the K/V stream is paid once per utterance instead of once per beam.
-template <int U, bool NT, bool KVH, bool PIPE = false, bool ALIVE = false, int NTHR = 256, bool SLOT = false, bool ANC = false, int G = 1>
+// QCAP (token-level timestamps, cross attention): the block of split 0 of a selected head stores its finished query into the history
+// buffer p.qh at row st->step -- one stream's lanes, plain 16-byte vector stores -- before a finished row would leave; a compile-time form,
+// the other instantiations are untouched.
+template <int U, bool NT, bool KVH, bool PIPE = false, bool ALIVE = false, int NTHR = 256, bool SLOT = false, bool ANC = false, int G = 1,
+          bool QCAP = false>
 __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
     constexpr int LPK = KVH ? 8 : 16;          // lanes per key
     constexpr int DPL = HEAD_DIM / LPK;        // head dims per lane: 8 or 4 (16 bytes of K or V either way)
@@ -808,6 +812,17 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
         const float rstd = rsqrtf(wave_allreduce_sum_d(sq) / d + 1e-5f);
 #pragma unroll
         for (int i = 0; i < DPL; ++i) q[g][i] = (q[g][i] - mean * r[i]) * rstd + t[i];
+        }
+    }
+    if constexpr (QCAP) {
+        static_assert(G == 1, "the query capture is a form of the plain cross attention");
+        if (split == 0 && sid == 0) {
+            const int sel = p.qh_sel[h], step = p.st->step;
+            if (sel >= 0 && !p.st->done && step < p.qh_steps) {   // (steps enqueued past the stop test must not write)
+                float* dst = p.qh + (((size_t)sel * p.qh_rows + b) * p.qh_steps + step) * HEAD_DIM + DPL * c;
+#pragma unroll
+                for (int i = 0; i < DPL; i += 4) *reinterpret_cast<float4*>(dst + i) = make_float4(q[0][i], q[0][i + 1], q[0][i + 2], q[0][i + 3]);
+            }
         }
     }
     // A finished row pads whatever it computes (run.py:219-226 stops a batch-1 decode at its own EOS): in the step graph that
@@ -1006,6 +1021,17 @@ hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s) {
     // (sixteen-wave blocks measured SLOWER than eight: cross-attention 19.2 -> 20.6 us, self-attention at 224 keys 5.9 -> 6.4)
     // (and four keys per stream and iteration stay best in the eight-wave form: U = 2 / 4 / 8 -> 19.9 / 19.8 / 20.1 us cross-attention,
     //  6.3 / 5.8 / 6.0 us self-attention at 224 keys)
+    if (p.qh) {   // token-level timestamps: the cross-attention launches of the step graph, in the default block shapes of the plain forms
+        if (p.group > 1 || p.anc || p.slot_row || p.alive || !p.qh_sel || !p.st || !p.ln_h || p.fixed_len <= 0) return hipErrorInvalidValue;
+        if (!p.kv_half) {
+            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, false, 1, true>), grid, dim3(512), 0, s, p);
+            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, false, 1, true>), grid, dim3(512), 0, s, p);
+        } else {
+            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, false, 1, true>), grid, dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, false, 1, true>), grid, dim3(256), 0, s, p);
+        }
+        return hipGetLastError();
+    }
     if (p.group > 1) {   // beam search, cross attention, grouped form: grid z = utterances, `group` query rows per block
         if (p.anc || p.alive || p.slot_row || p.B % p.group != 0 || (p.group != 2 && p.group != 4)) return hipErrorInvalidValue;
         const dim3 gg(p.n_split, p.H, p.B / p.group);

@@ -138,7 +138,53 @@ struct DecAttnParams {
     // beam search, cross attention, grouped form (2 or 4; 0 / 1: off): cache row u is shared by the query rows u * group .. + group - 1,
     // one block streams it once for all of them (grid z = B / group).  Not with slot_row / alive / anc.
     int group;
+    // token-level timestamps (wt_decoder_set_token_timestamps), cross attention only: the blocks of split 0 whose head h has qh_sel[h] >= 0
+    // store the finished query (after the folded-LayerNorm finish) into qh[qh_sel[h]][b][st->step][64], before a finished row leaves.
+    // qh == nullptr: the instantiations without the capture run, exactly as before.
+    float* qh;             // [n_sel][qh_rows][qh_steps][64]
+    const int* qh_sel;     // this layer's [H]: selection index of head h, or -1
+    int qh_rows, qh_steps;
 };
+
+// ---- token-level timestamps: the post-pass over the captured queries and the resident cross-K cache (kernels_token_timestamps.hip) ----
+// Per utterance b and selected head: W[t][s] = softmax_s(q_hist[t] . K[s]); W = (W - mean_t) / std_t (population std over the N tokens);
+// a median of odd `width` along s with reflect padding (the input unchanged when S <= width / 2); the mean over the heads = matrix[N][S];
+// DTW on -matrix with an fp32 cost, cell = (float)((double)(-m) + (double)c), predecessor 0 (diagonal) if c0 < c1 && c0 < c2, else 1 (up)
+// if c1 < c0 && c1 < c2, else 2 (left); backtrace from (N, S) with the borders trace[0][:] = 2, trace[:][0] = 1;
+// out[b][0] = 0, out[b][1 + k] = (float)(time_precision * frame at which the path first reaches token k).
+constexpr int TT_MAX_HEADS = 32;
+constexpr int TT_MAX_WIDTH = 15;
+constexpr int TT_MAX_TOKENS = 1024;   // N of one DTW workgroup (one thread per token row)
+struct TokTsParams {
+    const float* q_hist;   // [n_sel][qh_rows][qh_steps][64]
+    int qh_rows, qh_steps;
+    const void* cross_k;   // resident cross-K caches [L][cross_rows][H][S][64], float or IEEE half (kv_half)
+    int kv_half, cross_rows, H, S;
+    int n_sel;
+    int layer[TT_MAX_HEADS], head[TT_MAX_HEADS];
+    int width;             // odd, 1 .. TT_MAX_WIDTH
+    double time_precision;
+    const DecState* st;    // N = st->cur_len[0] - 1 (the batch-wide length, as the reference), or, st == nullptr, n_fixed
+    int n_fixed, n_cap;    // n_cap: row capacity of W / matrix / trace and the grid's bound on N
+    int B;
+    float* W;              // scratch [n_sel][n_cap][S]: one utterance's softmax rows
+    float* mean;           // scratch [n_sel][S]
+    float* sdev;           // scratch [n_sel][S]
+    float* matrix;         // [B][n_cap][S]
+    uint8_t* trace;        // [B][n_cap][trace_ld]: predecessor codes of rows 1..N, columns 0..S (column 0 unused)
+    int trace_ld;          // multiple of 4, >= S + 1
+    int* path;             // optional [B][2][n_cap + S]: the path in backtrace order (text indices, then time indices)
+    int* path_len;         // optional [B]
+    float* out;            // [B][out_ld]
+    int out_ld;
+};
+inline int tt_trace_ld(int S) { return (S + 1 + 3) & ~3; }
+// one utterance's matrix (three launches: softmax rows, column statistics, median + head mean)
+hipError_t launch_tt_matrix(const TokTsParams& p, int b, hipStream_t s);
+// the median + head mean alone over p.W as it stands (p.mean == nullptr: W is taken as already normalised)
+hipError_t launch_tt_median(const TokTsParams& p, int b, hipStream_t s);
+// DTW + backtrace + timestamps of all B utterances (one workgroup each)
+hipError_t launch_tt_dtw(const TokTsParams& p, hipStream_t s);
 
 // A/B tuning switches (WT_NSPLIT_CROSS, WT_GEMM_NO_DMA, ...; DESIGN.md "Tuning knobs") are lab tools, not part of the C-ABI's
 // contract: they are read ONLY when the process also sets WT_TUNING=1, so a stray variable in a production environment cannot

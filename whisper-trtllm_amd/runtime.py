@@ -219,6 +219,31 @@ def _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step,
         raise ValueError("beam search does not take logits_trace / force_eos_step(s)")
 
 
+def _check_token_timestamp_args(config, info, return_token_timestamps, alignment_heads, median_filter_width, num_beams):
+    """Token-level timestamps: the head list to use ([] when the mode is off).  `alignment_heads` of the call wins over the config's
+    (generation_config.json's `alignment_heads`, which examples/whisper/_common.py copies into the config).  Refused before anything is
+    enqueued: no heads, heads outside the model, more than 32, a listed-twice head, an even or out-of-range width, beam search."""
+    if not return_token_timestamps:
+        return []
+    heads = alignment_heads if alignment_heads is not None else config.get("alignment_heads")
+    if not heads:
+        raise ValueError("Model generation config has no `alignment_heads`, token-level timestamps not available. "
+                         "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this property to the generation config.")
+    if num_beams > 1:
+        raise ValueError("beam search and token-level timestamps cannot be combined (they would need beam_indices, which the engine does not keep)")
+    heads = [(int(l), int(h)) for l, h in heads]
+    if len(heads) > 32:
+        raise ValueError(f"at most 32 alignment heads, got {len(heads)}")
+    for l, h in heads:
+        if not (0 <= l < info.n_layers and 0 <= h < info.n_heads):
+            raise ValueError(f"alignment head ({l}, {h}) outside {info.n_layers} layers x {info.n_heads} heads")
+    if len(set(heads)) != len(heads):
+        raise ValueError("an alignment head is listed twice")
+    if not isinstance(median_filter_width, int) or median_filter_width < 1 or median_filter_width > 15 or median_filter_width % 2 != 1:
+        raise ValueError(f"`median_filter_width` should be an odd number in [1, 15], got {median_filter_width!r}")
+    return heads
+
+
 class WhisperDecoderEngine:
     """Greedy decode with the KV cache resident on the device (no per-token host round trip).
 
@@ -282,15 +307,66 @@ class WhisperDecoderEngine:
         _lib.check(self.session._lib.wt_decoder_set_beam_search(self.session.handle, ctypes.byref(b) if b is not None else None),
                    "wt_decoder_set_beam_search")
 
+    def _set_token_timestamps(self, heads=(), median_filter_width: int = 7, time_precision: float = 0.02):
+        t = None
+        if heads:
+            arr, n = _i32_array([x for pair in heads for x in pair])
+            self._tt_keep = arr
+            t = _lib.TokenTimestampParams(n // 2, ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32)), int(median_filter_width), float(time_precision))
+        _lib.check(self.session._lib.wt_decoder_set_token_timestamps(self.session.handle, ctypes.byref(t) if t is not None else None),
+                   "wt_decoder_set_token_timestamps")
+        self._tt_heads = list(heads)
+
+    def read_token_timestamps(self, cur_len: int):
+        """Token-level timestamps of the decode in flight (wt_decoder_read_token_timestamps: the cross-attention DTW post-pass on the
+        device, stream-ordered): float32 [B, cur_len] seconds on the GPU, entry 0 of a row is 0."""
+        import torch
+        ml = self._p.max_length
+        buf = torch.empty(self._B, ml, dtype=torch.float32, device=self._enc.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_decoder_read_token_timestamps(self.session.handle, buf.data_ptr(), ml, ctypes.c_void_p(stream)),
+                   "wt_decoder_read_token_timestamps")
+        return buf[:, :cur_len].clone()
+
+    def token_timestamp_q_hist(self):
+        """Debug read-back: the captured cross-attention queries, float32 [heads, B, max_length - 1, 64] on the GPU."""
+        import torch
+        out = torch.empty(len(self._tt_heads), self._B, self._p.max_length - 1, 64, dtype=torch.float32, device=self._enc.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_dbg_token_timestamp_q_hist(self.session.handle, out.data_ptr(), ctypes.c_void_p(stream)), "wt_dbg_token_timestamp_q_hist")
+        return out
+
+    def token_timestamp_matrix(self):
+        """Debug read-back after `read_token_timestamps`: the DTW's input, float32 [B, max_length - 1, S] on the GPU (rows < cur_len - 1 valid)."""
+        import torch
+        out = torch.empty(self._B, self._p.max_length - 1, self.session.info.max_source_positions, dtype=torch.float32, device=self._enc.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_dbg_token_timestamp_matrix(self.session.handle, out.data_ptr(), ctypes.c_void_p(stream)), "wt_dbg_token_timestamp_matrix")
+        return out
+
+    def cross_k_head(self, layer: int, head: int):
+        """Debug read-back: the resident cross-K rows of (layer, head), numpy float32 [B, S, 64] (fp16 engines: widened)."""
+        import numpy as np
+        import torch
+        out = np.empty((self._B, self.session.info.max_source_positions, 64), dtype=np.float32)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_dbg_cross_k_head(self.session.handle, layer, head, out.ctypes.data, ctypes.c_void_p(stream)), "wt_dbg_cross_k_head")
+        return out
+
     def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
-              return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False):
+              return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
+              return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7):
         """Start a decode (wt_decoder_begin).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
         the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
         `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
-        (False or True); utterances x num_beams <= 16 rows per call; not together with timestamps, logits_trace or force_eos_step(s)."""
+        (False or True); utterances x num_beams <= 16 rows per call; not together with timestamps, logits_trace or force_eos_step(s).
+        `return_token_timestamps`: per-token times by cross-attention DTW on the device (wt_decoder_set_token_timestamps; read them with
+        `read_token_timestamps`), over `alignment_heads` [(layer, head), ...] (default: the config's) with transformers'
+        `median_filter_width`; batch decodes only, not with beams; every row uses the batch-wide token length, as the reference."""
         import torch
         _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps)
         i = self.session.info
+        tt_heads = _check_token_timestamp_args(self.config, i, True, alignment_heads, median_filter_width, num_beams) if return_token_timestamps else []
         if encoder_hidden.dtype != torch.float32 or tuple(encoder_hidden.shape[1:]) != (i.max_source_positions, i.d_model):
             raise ValueError(f"encoder_hidden must be float32 [B,{i.max_source_positions},{i.d_model}]")
         if not encoder_hidden.is_cuda or (logits_trace is not None and not logits_trace.is_cuda):
@@ -303,6 +379,7 @@ class WhisperDecoderEngine:
         self._trace = logits_trace
         self._set_timestamp_rules(return_timestamps)
         self._set_beam_search(num_beams, length_penalty, early_stopping)
+        self._set_token_timestamps(tt_heads, median_filter_width)
         self._beams = int(num_beams) if num_beams > 1 else 1
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.session._lib.wt_decoder_begin(self.session.handle, self._enc.data_ptr(), self._B, ctypes.byref(self._p),
@@ -366,16 +443,22 @@ class WhisperDecoderEngine:
 
     def generate(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, chunk: int = 0, force_eos_steps=None,
                  lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping=False, return_scores: bool = False):
+                 early_stopping=False, return_scores: bool = False, return_token_timestamps: bool = False, alignment_heads=None,
+                 median_filter_width: int = 7):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
         `return_timestamps`: timestamp mode (see `begin`).  `num_beams` > 1: beam search (see `begin`), the best hypothesis per
         utterance; `return_scores`: (ids, float32 sequence scores [B]) -- beam search only.
 
         Default (`chunk` 0): the stop test is followed through the engine's host mailbox (`run`), at most `lookahead` steps are
-        enqueued past the stop.  `chunk` > 0 selects the older protocol -- `chunk` steps between two synchronising polls."""
+        enqueued past the stop.  `chunk` > 0 selects the older protocol -- `chunk` steps between two synchronising polls.
+        `return_token_timestamps`: returns (ids, float32 token timestamps [B, len] in seconds) -- see `begin`."""
         _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps)
         if return_scores and num_beams <= 1:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence score)")
+        tt = None
+        if return_token_timestamps:
+            _check_token_timestamp_args(self.config, self.session.info, True, alignment_heads, median_filter_width, num_beams)
+            tt = {"return_token_timestamps": True, "alignment_heads": alignment_heads, "median_filter_width": median_filter_width}
         group = self.max_batch // max(int(num_beams), 1)
         if num_beams > 1 and encoder_hidden.shape[0] > group:   # utterances x beams <= 16 rows per engine call
             import torch
@@ -403,24 +486,26 @@ class WhisperDecoderEngine:
                 raise ValueError(f"logits_trace supports at most {self.max_batch} utterances per call")
             parts = [self.generate(encoder_hidden[i:i + self.max_batch], max_length, force_eos_step, None, chunk,
                                    None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead,
-                                   return_timestamps)
+                                   return_timestamps, **(tt or {}))
                      for i in range(0, encoder_hidden.shape[0], self.max_batch)]
-            width = max(p.shape[1] for p in parts)
             pad = self.config["pad_token_id"]
-            parts = [torch.nn.functional.pad(p, (0, width - p.shape[1]), value=pad) for p in parts]
-            return torch.cat(parts, dim=0)
-        self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps)
+            cat = lambda ps, value: torch.cat([torch.nn.functional.pad(p, (0, max(q.shape[1] for q in ps) - p.shape[1]), value=value) for p in ps], dim=0)
+            if tt:      # every engine batch ran to its own length: its rows' times are those of that length
+                return cat([p[0] for p in parts], pad), cat([p[1] for p in parts], 0.0)
+            return cat(parts, pad)
+        self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, **(tt or {}))
         if chunk <= 0:
             cur, _nu = self.run(lookahead)
-            return self.read_ids(cur)
-        cur, done = 1, False
-        ml = self._p.max_length
-        while not done and cur < ml:
-            self.steps(min(chunk, ml - cur))
-            cur, _nu, done = self.poll()
-        return self.read_ids(cur)
+        else:
+            cur, done = 1, False
+            ml = self._p.max_length
+            while not done and cur < ml:
+                self.steps(min(chunk, ml - cur))
+                cur, _nu, done = self.poll()
+        return (self.read_ids(cur), self.read_token_timestamps(cur)) if tt else self.read_ids(cur)
 
-    def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1) -> "DecodeStream":
+    def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1,
+               return_token_timestamps: bool = False) -> "DecodeStream":
         """Open a continuous decode on this engine (wt_decoder_stream_*): `slots` rows stay busy, every utterance stops at its own EOS
         and its slot is refilled on the device within the same step.  Ends with the next `begin` / `generate` on this engine.
         The continuous mode has no timestamp mode: `return_timestamps=True` raises ValueError."""
@@ -428,6 +513,8 @@ class WhisperDecoderEngine:
             raise ValueError("timestamp mode is a batch-decode feature (generate / begin); the continuous mode does not predict timestamps")
         if num_beams > 1:
             raise ValueError("beam search is a batch-decode feature (generate / begin); the continuous mode decodes greedily")
+        if return_token_timestamps:
+            raise ValueError("token-level timestamps are a batch-decode feature (generate / begin); the continuous mode keeps no query history")
         return DecodeStream(self, slots, pool_rows, max_length)
 
     def set_profiling(self, enabled: bool):
@@ -477,6 +564,7 @@ class DecodeStream:
         self.max_length = int(self._p.max_length)
         dec._set_timestamp_rules(False)     # a timestamp decode before on this handle left the mode on
         dec._set_beam_search(1)             # ... and so did a beam decode
+        dec._set_token_timestamps(())       # ... and a decode with token-level timestamps
         self.pool_rows = int(pool_rows) if pool_rows else 4 * self.slots
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_decoder_stream_begin(self._h, self.slots, self.pool_rows, ctypes.byref(self._p), ctypes.c_void_p(stream)),

@@ -104,6 +104,94 @@ class WhisperTokenDecoder:
             last = cur
         return out
 
+    # ---- word grouping for token-level timestamps (the reference's _combine_tokens_into_words and helpers,
+    # tokenization_whisper.py:1087-1215), space-separated languages
+    def _split_on_unicode(self, ids: List[int]):
+        """Cut wherever the tokens so far decode to complete unicode code points (_split_tokens_on_unicode)."""
+        full = self.decode_with_timestamps(ids)
+        bad = "\ufffd"
+        words, word_tokens, indices, cur, cur_idx, offset = [], [], [], [], [], 0
+        for k, tok in enumerate(ids):
+            cur.append(tok)
+            cur_idx.append(k)
+            text = self.decode_with_timestamps(cur)
+            if bad not in text or full[offset + text.index(bad)] == bad:
+                words.append(text)
+                word_tokens.append(cur)
+                indices.append(cur_idx)
+                cur, cur_idx = [], []
+                offset += len(text)
+        return words, word_tokens, indices
+
+    def _split_on_spaces(self, ids: List[int]):
+        """Join the unicode pieces into words at leading spaces, punctuation and special tokens (_split_tokens_on_spaces)."""
+        eos = self.eos_token_id
+        words, word_tokens, indices = [], [], []
+        for sub, toks, idx in zip(*self._split_on_unicode(ids)):
+            special = toks[0] >= eos
+            punctuation = sub.strip() in "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"
+            if special or sub.startswith(" ") or punctuation or not words:
+                words.append(sub)
+                word_tokens.append(list(toks))
+                indices.append(list(idx))
+            else:
+                words[-1] += sub
+                word_tokens[-1].extend(toks)
+                indices[-1].extend(idx)
+        return words, word_tokens, indices
+
+    @staticmethod
+    def _merge_punctuations(words, tokens, indices, prepended, appended):
+        i, j = len(words) - 2, len(words) - 1
+        while i >= 0:       # opening punctuation joins the word after it
+            if words[i].startswith(" ") and words[i].strip() in prepended:
+                words[j], tokens[j], indices[j] = words[i] + words[j], tokens[i] + tokens[j], indices[i] + indices[j]
+                words[i], tokens[i], indices[i] = "", [], []
+            else:
+                j = i
+            i -= 1
+        i, j = 0, 1
+        while j < len(words):   # closing punctuation joins the word before it
+            if not words[i].endswith(" ") and words[j] in appended:
+                words[i] += words[j]
+                tokens[i] += tokens[j]
+                indices[i] += indices[j]
+                words[j], tokens[j], indices[j] = "", [], []
+            else:
+                i = j
+            j += 1
+        words[:] = [w for w in words if w]
+        tokens[:] = [t for t in tokens if t]
+        indices[:] = [x for x in indices if x]
+
+    @property
+    def eos_token_id(self) -> int:
+        eot = [i for i, t in self.id_to_token.items() if t == "<|endoftext|>"]
+        if not eot:
+            raise ValueError("the vocabulary has no <|endoftext|> token")
+        return eot[0]
+
+    def combine_tokens_into_words(self, ids: Sequence[int], prepend_punctuations: str = "\"'\u201c\u00a1\u00bf([{-",
+                                  append_punctuations: str = "\"'.\u3002,\uff0c!\uff01?\uff1f:\uff1a\u201d)]}\u3001"):
+        """(words, token ids per word, token positions per word) of a space-separated language (_combine_tokens_into_words)."""
+        words, word_tokens, indices = self._split_on_spaces([int(i) for i in ids])
+        self._merge_punctuations(words, word_tokens, indices, prepend_punctuations, append_punctuations)
+        return words, word_tokens, indices
+
+    def words(self, ids: Sequence[int], token_timestamps: Sequence) -> List[dict]:
+        """[{"text", "timestamp": (start s, end s)}] per word (_collate_word_timestamps).  `token_timestamps` holds one entry per id:
+        either (start, end) pairs, or the start times `generate(..., return_token_timestamps=True)` returns -- a token then ends where
+        the next one starts, the last one where it starts.  Space-separated languages only."""
+        ids = [int(i) for i in ids]
+        ts = list(token_timestamps)
+        if len(ts) != len(ids):
+            raise ValueError(f"{len(ids)} ids but {len(ts)} token timestamps")
+        if ts and not isinstance(ts[0], (tuple, list)):
+            ts = [float(t) for t in ts]
+            ts = [(ts[k], ts[k + 1] if k + 1 < len(ts) else ts[k]) for k in range(len(ts))]
+        words, _tok, indices = self.combine_tokens_into_words(ids)
+        return [{"text": w, "timestamp": (ts[idx[0]][0], ts[idx[-1]][1])} for w, idx in zip(words, indices)]
+
     def batch_decode(self, batch: Iterable[Sequence[int]], skip_special_tokens: bool = True) -> List[str]:
         return [self.decode(ids, skip_special_tokens) for ids in batch]
 
