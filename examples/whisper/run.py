@@ -58,6 +58,11 @@ def parse_arguments():
     parser.add_argument("--median_filter_width", type=int, default=None, help="default: the config's median_filter_width, else 7")
     parser.add_argument("--num_beams", type=int, default=1, help="fast path: beam search on the device with this many beams (<= 8; batches are "
                         "sized so that utterances x beams <= 16 rows); needs a batch plan and no --return_timestamps")
+    parser.add_argument("--return_logprobs", action="store_true", help="fast path: token log-probabilities from the device; prints avg_logprob, "
+                        "no_speech_prob (with --no_speech_token_id) and the compression ratio per utterance, and each word's mean token "
+                        "log-probability with --return_token_timestamps; needs a batch plan, no beams")
+    parser.add_argument("--no_speech_token_id", type=int, default=None, help="the <|nospeech|> (<|nocaptions|>) id whose first-step probability "
+                        "--return_logprobs reports as no_speech_prob")
     parser.add_argument("--length_penalty", type=float, default=1.0)
     parser.add_argument("--early_stopping", action="store_true")
     args = parser.parse_args()
@@ -69,6 +74,10 @@ def parse_arguments():
     if args.return_token_timestamps and (args.batching == "continuous" or args.num_beams > 1 or args.session):
         parser.error("--return_token_timestamps needs the fast path with a batch plan (--batching sorted | dataset) and no beams: the "
                      "continuous mode keeps no query history, beam search no beam_indices, the Session path no cross attentions")
+    if args.return_logprobs and (args.batching == "continuous" or args.num_beams > 1 or args.session):
+        parser.error("--return_logprobs needs the fast path with a batch plan (--batching sorted | dataset) and no beams")
+    if args.no_speech_token_id is not None and not args.return_logprobs:
+        parser.error("--no_speech_token_id needs --return_logprobs")
     if args.alignment_heads is not None:
         try:
             args.alignment_heads = [tuple(int(x) for x in pair.split(",")) for pair in args.alignment_heads]
@@ -200,7 +209,7 @@ if __name__ == "__main__":
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.time()
-            indexed = []
+            indexed, score_rows = [], []
             if groups is None:
                 rows = pipe.transcribe_continuous(torch.cat(mels[begin:end]), slots=8, chunk=8) if end > begin else []
                 indexed = list(zip(range(begin, end), [r.tolist() for r in rows]))
@@ -210,9 +219,17 @@ if __name__ == "__main__":
                     one = {"return_token_timestamps": True, "alignment_heads": args.alignment_heads, "return_timestamps": args.return_timestamps,
                            "median_filter_width": args.median_filter_width or int(config.get("median_filter_width", 7))}
                     kw = [one] * len(groups)
+                if args.return_logprobs:
+                    lp = {"return_logprobs": True, "no_speech_token_id": args.no_speech_token_id}
+                    kw = [dict(k, **lp) for k in (kw or [{}] * len(groups))]
                 if args.num_beams > 1:
                     kw = [{"num_beams": args.num_beams, "length_penalty": args.length_penalty, "early_stopping": args.early_stopping}] * len(groups)
                 for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):
+                    if args.return_logprobs:             # (ids, [seconds per token,] DecodeScores) of the batch
+                        sc = ids[-1]
+                        nsp = sc.no_speech_prob.cpu().tolist() if sc.no_speech_prob is not None else [None] * len(g)
+                        score_rows += list(zip(g, zip(sc.token_logprobs.cpu().tolist(), sc.avg_logprob.cpu().tolist(), nsp)))
+                        ids = ids[:-1] if args.return_token_timestamps else ids[0]
                     if args.return_token_timestamps:     # (ids, seconds per token) of the batch
                         indexed += list(zip(g, zip(ids[0].cpu().tolist(), ids[1].cpu().tolist())))
                     else:
@@ -224,6 +241,8 @@ if __name__ == "__main__":
                 results["token_timestamps"] = [row[1] for row in ids]
                 ids = [row[0] for row in ids]
             results["fast"] = (elapsed, ids)
+            if args.return_logprobs:
+                results["scores"] = [row for _, row in sorted(tensorrt_llm.sharding.gather_objects(score_rows, dist))]
         if rank == 0:
             print(f"fast path   : {results['fast'][0]:.3f} s for {len(mels)} x 30 s on {world} rank(s)  ({30 * len(mels) / results['fast'][0]:.1f} audio-s/s)")
             if args.dump_ids:
@@ -245,6 +264,7 @@ if __name__ == "__main__":
         diff = [(x, y) for x, y in zip(a, b) if x != y]
         print(f"Compare Result: same [{len(a) - len(diff)}], diff [{len(diff)}]")
     token_times = results.pop("token_timestamps", None)
+    scores = results.pop("scores", None)
     if rank == 0:
         for key in results:
             print(key, "ids[0][:16] =", results[key][1][0][:16])
@@ -256,8 +276,12 @@ if __name__ == "__main__":
                 for seg in tok.offsets(ids):
                     print(f"  [{seg['timestamp'][0]:6.2f} --> {seg['timestamp'][1]:6.2f}] {seg['text']}")
             if token_times is not None:
-                for w in tok.words(ids, token_times[args.audio.index(path)]):
-                    print(f"  [{w['timestamp'][0]:6.2f} --> {w['timestamp'][1]:6.2f}] {w['text']!r}")
+                word_lp = [None] * len(ids)
+                if scores is not None:      # each word's mean token log-probability
+                    lps = scores[args.audio.index(path)][0]
+                    word_lp = [sum(lps[k] for k in idx) / len(idx) for idx in tok.combine_tokens_into_words([int(i) for i in ids])[2]]
+                for w, lp in zip(tok.words(ids, token_times[args.audio.index(path)]), word_lp):
+                    print(f"  [{w['timestamp'][0]:6.2f} --> {w['timestamp'][1]:6.2f}] {w['text']!r}" + (f"  logprob {lp:.3f}" if lp is not None else ""))
     elif rank == 0 and token_times is not None:      # no tokenizer: every token as its own word
         eos, pad = config["eos_token_id"], config["pad_token_id"]
         for i, (ids, ts) in enumerate(list(zip(results["fast"][1], token_times))[:4]):
@@ -268,6 +292,14 @@ if __name__ == "__main__":
         tb = tensorrt_llm.runtime.timestamp_rules(config)[1]
         for i, ids in enumerate(next(iter(results.values()))[1][:4]):
             print(f"utterance {i}:", " ".join(f"<|{(t - tb) * 0.02:.2f}|>" if t >= tb else str(t) for t in ids))
+    if rank == 0 and scores is not None:             # confidence per utterance (openai-whisper's segment fields)
+        tok = tensorrt_llm.text.WhisperTokenDecoder.from_dir(args.whisper) if os.path.isdir(args.whisper) else None
+        eos, pad = config["eos_token_id"], config["pad_token_id"]
+        for i, (ids, (_lps, avg, nsp)) in enumerate(zip(results["fast"][1], scores)):
+            # without a tokenizer the ratio is taken over the ids written out: repetition still shows
+            text = tok.decode(ids, skip_special_tokens=True) if tok else " ".join(str(t) for t in trim_after_eos(ids, eos, pad))
+            ratio = tensorrt_llm.text.compression_ratio(text) if text else 0.0
+            print(f"utterance {i}: avg_logprob {avg:.6f}  no_speech_prob {'n/a' if nsp is None else format(nsp, '.6f')}  compression_ratio {ratio:.3f}")
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

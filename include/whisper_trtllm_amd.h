@@ -238,6 +238,29 @@ typedef struct {
 int wt_decoder_set_token_timestamps(wt_engine* dec, const wt_token_timestamp_params* t);
 int wt_decoder_read_token_timestamps(wt_engine* dec, float* out, int ld, void* stream);
 
+/* (9e) token log-probabilities for the batch decode (wt_decoder_begin / _steps / _run / _greedy), on the device and without another
+ * launch: the log-sum-exp of a step's scores is carried beside the running argmax of the vocabulary projection, so the logits still never
+ * reach memory.  With s = the step's scores after every processor it applies (Suppress -> SuppressAtBegin -> Force -> the timestamp rules
+ * in timestamp mode), the step that writes position t of row b stores token_logprob[b][t] = s[tok] - logsumexp(s) over the entries that
+ * are not -inf (transformers' compute_transition_scores(normalize_logits=True)): exactly 0 at a forced position (forced_decoder_ids and
+ * the timestamp mode's <|0.00|>), NaN when a surviving score is NaN, the EOS score of the step where force_eos_step(s) replaced the token.
+ * Position 0 and the positions behind a row's EOS are 0; the EOS itself is scored.  sum_logprob[b] is the fp32 sum of the row's entries
+ * through its EOS, accumulated in step order (openai-whisper's avg_logprob = sum_logprob / number of scored positions).  With
+ * no_speech_token_id >= 0, no_speech_prob[b] = softmax(raw logits of step 0)[no_speech_token_id], over the UNPROCESSED logits of the
+ * step whose input is the start token (-1: off).
+ * wt_decoder_read_logprobs copies them out, stream-ordered, at any point of the decode: token_logprobs DEVICE float [batch][ld], ld >=
+ * max_length; sum_logprob DEVICE float [batch]; no_speech_prob DEVICE float [batch] or NULL.  WT_E_STATE without a decode in this mode.
+ * The setting applies from the next wt_decoder_begin on this handle (which clears the buffers); p == NULL or enabled == 0 turns it off,
+ * and the engine then enqueues exactly what it did before.  WT_E_INVALID for a no_speech_token_id outside [-1, V); wt_decoder_begin refuses
+ * (WT_E_UNSUPPORTED) the mode together with beam search (wt_decoder_read_beam_scores is its score), and wt_decoder_stream_begin refuses
+ * it.  It combines with the timestamp mode (9b), token-level timestamps (9d), logits_trace and force_eos_step(s). */
+typedef struct {
+    int32_t enabled;
+    int32_t no_speech_token_id;      /* -1: no no_speech_prob */
+} wt_logprob_params;
+int wt_decoder_set_logprobs(wt_engine* dec, const wt_logprob_params* p);
+int wt_decoder_read_logprobs(wt_engine* dec, float* token_logprobs, int ld, float* sum_logprob, float* no_speech_prob, void* stream);
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

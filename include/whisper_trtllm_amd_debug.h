@@ -186,6 +186,19 @@ int wt_dbg_greedy_select(const float* logits, const float* part_val, const int32
                          const int32_t* forced, int32_t* ids, int32_t* unfinished, int32_t* state, int force_eos_step,
                          const int32_t* force_eos_rows, const void* tok_emb, const float* pos_emb, int pos_rows, int emb_half, float* next_x, int B,
                          int V, int d, int max_length, int begin_index, int eos, int pad, void* scratch, void* stream);
+/* The greedy tail of the log-probability mode (wt_decoder_set_logprobs) on caller-supplied operands, through the engine's own launch
+ * builders.  form 0: the vocabulary GEMV with the log-sum-exp epilogue over X [B][K] (plain activations, no LayerNorm) and W [V][K] (float),
+ * then greedy_finish_kernel<false, true>; form 1: greedy_select_kernel<true> over `logits` [B][V], then the same finish kernel; form 2:
+ * timestamp mode, ts_select_kernel<true> + greedy_finish_kernel<true, true> over `logits` with the rules `t`.  mask bytes [V] (device; bit 0
+ * suppressed, bit 1 suppressed at begin_index), forced a HOST array [max_length], ids int32 [B][max_length] (device; position cur_len is
+ * written), cur_len: every row's length (1 <= cur_len < max_length), step: DecState.step (no_speech_prob is stored at step 0 only),
+ * no_speech_token_id < 0: off.  Outputs (device): logprob_out f32 [B] = the step's token_logprob, sum_out f32 [B] (starts at 0),
+ * no_speech_out f32 [B] or NULL.  scratch: wt_dbg_logprob_select_scratch_bytes(B, V, max_length) bytes.  Synchronises `stream`. */
+size_t wt_dbg_logprob_select_scratch_bytes(int B, int V, int max_length);
+int wt_dbg_logprob_select(int form, const float* X, const float* W, int K, const float* logits, const unsigned char* mask, const int32_t* forced,
+                          int32_t* ids, int B, int V, int max_length, int cur_len, int step, int begin_index, int eos, int force_eos_step,
+                          const wt_timestamp_params* t, int no_speech_token_id, float* logprob_out, float* sum_out, float* no_speech_out,
+                          void* scratch, void* stream);
 /* step 0's input: x[b] = tok_emb[ids[b][cur_len[b] - 1]] + pos_emb[pos[b]]; ids [B][ids_ld], cur_len, pos: HOST arrays; tok_emb [V][d] float
  * or half (emb_half), pos_emb [pos_rows][d].  scratch: wt_dbg_dec_embed_scratch_bytes(B, ids_ld) bytes. */
 size_t wt_dbg_dec_embed_scratch_bytes(int B, int ids_ld);

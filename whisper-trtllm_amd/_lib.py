@@ -18,7 +18,7 @@ EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
     "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores",
-    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
     "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_last_error", "wt_abi_version",
 ]
@@ -34,7 +34,8 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_dec_embed",
                  "wt_dbg_token_timestamps_scratch_bytes", "wt_dbg_token_timestamp_matrix_kernels", "wt_dbg_token_timestamp_median",
                  "wt_dbg_token_timestamp_dtw", "wt_dbg_token_timestamp_q_hist", "wt_dbg_token_timestamp_matrix", "wt_dbg_cross_k_head",
-                 "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes"]
+                 "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes",
+                 "wt_dbg_logprob_select_scratch_bytes", "wt_dbg_logprob_select"]
 
 
 class TensorDesc(Structure):
@@ -69,6 +70,10 @@ class BeamParams(Structure):
 
 class TokenTimestampParams(Structure):
     _fields_ = [("n_heads", c_int32), ("heads", POINTER(c_int32)), ("median_filter_width", c_int32), ("time_precision", c_double)]
+
+
+class LogprobParams(Structure):
+    _fields_ = [("enabled", c_int32), ("no_speech_token_id", c_int32)]
 
 
 class KernelTimer(Structure):
@@ -121,6 +126,8 @@ def load():
     lib.wt_decoder_read_beam_scores.argtypes = [c_void_p, c_void_p, c_void_p]
     lib.wt_decoder_set_token_timestamps.argtypes = [c_void_p, POINTER(TokenTimestampParams)]
     lib.wt_decoder_read_token_timestamps.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
+    lib.wt_decoder_set_logprobs.argtypes = [c_void_p, POINTER(LogprobParams)]
+    lib.wt_decoder_read_logprobs.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -197,6 +204,9 @@ def load():
     lib.wt_dbg_token_timestamp_postpass.argtypes = [c_void_p, I, P]
     lib.wt_dbg_token_timestamp_bytes.argtypes = [c_void_p]
     lib.wt_dbg_token_timestamp_bytes.restype = c_size_t
+    lib.wt_dbg_logprob_select_scratch_bytes.argtypes = [I, I, I]
+    lib.wt_dbg_logprob_select_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_logprob_select.argtypes = [I, P, P, I, P, P, POINTER(c_int32), P, I, I, I, I, I, I, I, I, POINTER(TimestampParams), I, P, P, P, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

@@ -146,6 +146,11 @@ struct wt_engine {
     // decode in flight (enabled == 0: off)
     wt_timestamp_params ts_req = {0, 0, 0, 0, 0}, ts_cur = {0, 0, 0, 0, 0};
     TsPart* ts_part = nullptr;    // scratch [dec_cap][SELECT_CHUNKS] of ts_select_kernel
+    // log-probability mode: the setting wt_decoder_set_logprobs asked for (applied by the next wt_decoder_begin) and that of the decode in
+    // flight (enabled == 0: off); the partial pairs of the step and the three result buffers
+    wt_logprob_params lp_req = {0, -1}, lp_cur = {0, -1};
+    float4* lp_part = nullptr;    // [dec_cap][SEL_PARTS_CAP]
+    float *lp_side = nullptr, *lp_tok = nullptr, *lp_sum = nullptr, *lp_nsp = nullptr;   // [dec_cap][2], [dec_cap][cap_len], [dec_cap], [dec_cap]
     // beam search: the setting wt_decoder_set_beam_search asked for (applied by the next wt_decoder_begin) and that of the decode in
     // flight (num_beams <= 1: off).  In a beam decode B = beam_U * num_beams rows.
     wt_beam_params beam_req = {1, 1.f, 0}, beam_cur = {1, 1.f, 0};
@@ -687,6 +692,8 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     const size_t o_st = take(sizeof(DecState)), o_ids = take((size_t)B * cap_len * 4), o_unf = take((size_t)B * 4);
     const size_t o_forced = take((size_t)(cap_len + 1) * 4), o_mask = take((size_t)e->V), o_frows = take(16 * 4);
     const size_t o_tsp = take((size_t)B * SELECT_CHUNKS * sizeof(TsPart));
+    const size_t o_lpp = take((size_t)B * SEL_PARTS_CAP * sizeof(float4)), o_lps = take((size_t)B * 2 * 4), o_lpt = take((size_t)B * cap_len * 4);
+    const size_t o_lpsum = take((size_t)B * 4), o_lpn = take((size_t)B * 4);
     // beam search state (BeamParams): sized for MAX_ROWS rows whatever B, it is small
     const size_t o_bpart = take((size_t)MAX_ROWS * SELECT_CHUNKS * sizeof(BeamPart)), o_bsc = take(MAX_ROWS * 4), o_bids2 = take((size_t)MAX_ROWS * cap_len * 4);
     const size_t o_banc = take((size_t)2 * MAX_ROWS * cap_len * 4), o_burow = take(MAX_ROWS * 4), o_bhn = take(MAX_ROWS * 4), o_bhd = take(MAX_ROWS * 4);
@@ -699,6 +706,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     e->dh = (float*)(b + o_h); e->dh2 = (float*)(b + o_h2); e->dq = (float*)(b + o_q); e->datt = (float*)(b + o_att); e->att_cnt = (int*)(b + o_cnt); e->sel_val = (float*)(b + o_selv); e->sel_idx = (int*)(b + o_seli); e->dffn = (float*)(b + o_f); e->part = (float*)(b + o_part);
     e->logits = (float*)(b + o_lg); e->st = (DecState*)(b + o_st); e->ids = (int*)(b + o_ids); e->unfinished = (int*)(b + o_unf);
     e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows); e->ts_part = (TsPart*)(b + o_tsp);
+    e->lp_part = (float4*)(b + o_lpp); e->lp_side = (float*)(b + o_lps); e->lp_tok = (float*)(b + o_lpt); e->lp_sum = (float*)(b + o_lpsum); e->lp_nsp = (float*)(b + o_lpn);
     {
         BeamParams& bp = e->beam_dev;
         memset(&bp, 0, sizeof bp);
@@ -1129,6 +1137,24 @@ extern "C" int wt_decoder_set_token_timestamps(wt_engine* e, const wt_token_time
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_logprobs(wt_engine* e, const wt_logprob_params* p) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_logprobs: not a decoder engine");
+    if (!p || !p->enabled) {
+        e->lp_req = wt_logprob_params{0, -1};
+        return WT_OK;
+    }
+    if (p->no_speech_token_id < -1 || p->no_speech_token_id >= e->V)
+        return fail(WT_E_INVALID, "wt_decoder_set_logprobs: no_speech_token_id %d outside [-1, V=%d)", p->no_speech_token_id, e->V);
+    e->lp_req = wt_logprob_params{1, p->no_speech_token_id};
+    return WT_OK;
+}
+
+// the log-probability setting of the decode that is starting (a changed one re-captures the step graphs)
+static void lp_apply(wt_engine* e, const wt_logprob_params lp) {
+    if (memcmp(&e->lp_cur, &lp, sizeof lp) != 0) e->graph_valid = false;
+    e->lp_cur = lp;
+}
+
 static void fill_select_params(wt_engine* e, SelectParams& sp);
 
 extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, const wt_greedy_params* p, void* stream) {
@@ -1143,6 +1169,8 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
             return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token-level timestamps cannot be combined (no beam_indices)");
         if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
             return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: logits_trace / force_eos_step(s) are not available with beam search");
+        if (e->lp_req.enabled)
+            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token log-probabilities cannot be combined (wt_decoder_read_beam_scores is the beams' score)");
         if (U * nb > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", U, nb, MAX_ROWS);
         B = U * nb;
     }
@@ -1152,6 +1180,13 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
     int rc = decode_setup(e, B, p, 0, false, s, "wt_decoder_begin", nb > 1 ? beam : wt_beam_params{1, 1.f, 0});
     if (rc) return rc;
     e->beam_U = U;
+    lp_apply(e, e->lp_req);
+    if (e->lp_cur.enabled) {   // position 0, the positions behind an EOS and the sums start at zero
+        HIPCHK(hipMemsetAsync(e->lp_tok, 0, (size_t)B * p->max_length * 4, s));
+        HIPCHK(hipMemsetAsync(e->lp_sum, 0, (size_t)B * 4, s));
+        HIPCHK(hipMemsetAsync(e->lp_nsp, 0, (size_t)B * 4, s));
+        HIPCHK(hipMemsetAsync(e->lp_side, 0, (size_t)B * 2 * 4, s));
+    }
     LAUNCH(launch_dec_init(e->st, e->ids, e->unfinished, B, p->max_length, p->decoder_start_token_id, e->epoch, s));
     if (nb > 1) {
         SelectParams sp;
@@ -1181,6 +1216,10 @@ static void fill_select_params(wt_engine* e, SelectParams& sp) {
         sp.beam_on = 1; sp.beam = e->beam_dev;
         sp.beam.nb = e->beam_cur.num_beams; sp.beam.U = e->beam_U; sp.beam.length_penalty = e->beam_cur.length_penalty;
         sp.beam.early_stopping = e->beam_cur.early_stopping;
+    }
+    if (e->lp_cur.enabled && !e->stream_mode) {
+        sp.lp_on = 1; sp.lp_ns = e->lp_cur.no_speech_token_id; sp.lp_part = e->lp_part; sp.lp_side = e->lp_side; sp.lp_tok = e->lp_tok;
+        sp.lp_sum = e->lp_sum; sp.lp_nsp = e->lp_nsp;
     }
     if (e->stream_mode) {
         sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1; sp.force_eos_rows = nullptr; sp.trace = nullptr;
@@ -1284,6 +1323,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: timestamp mode is a batch-decode feature (wt_decoder_begin)");
     if (e->beam_req.num_beams > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: beam search is a batch-decode feature (wt_decoder_begin)");
     if (e->tt_req.n_sel > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token-level timestamps are a batch-decode feature (wt_decoder_begin)");
+    if (e->lp_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token log-probabilities are a batch-decode feature (wt_decoder_begin)");
     if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);
@@ -1291,6 +1331,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     hipStream_t s = (hipStream_t)stream;
     int rc = decode_setup(e, slots, p, pool_rows, true, s, "wt_decoder_stream_begin");
     if (rc) return rc;
+    lp_apply(e, wt_logprob_params{0, -1});
     if (pool_rows > e->h_pool_cap || e->dec_maxlen_cap > e->h_ml_cap) {   // pinned report area: ids and final lengths per pool row
         HIPCHK(hipStreamSynchronize(s));   // no step of an earlier stream may still write the old area
         const int rows = pool_rows > e->h_pool_cap ? pool_rows : e->h_pool_cap;
@@ -1552,6 +1593,22 @@ extern "C" int wt_decoder_read_beam_scores(wt_engine* e, float* scores_out, void
     fill_select_params(e, sp);
     LAUNCH(launch_beam_finalize(sp, (hipStream_t)stream));
     HIPCHK(hipMemcpyAsync(scores_out, e->beam_dev.out_scores, (size_t)e->beam_U * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return WT_OK;
+}
+
+extern "C" int wt_decoder_read_logprobs(wt_engine* e, float* token_logprobs, int ld, float* sum_logprob, float* no_speech_prob, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->stream_mode || !e->lp_cur.enabled)
+        return fail(WT_E_STATE, "wt_decoder_read_logprobs: no decode with token log-probabilities in flight (wt_decoder_set_logprobs, then wt_decoder_begin)");
+    if (!token_logprobs || !sum_logprob || ld < e->max_length)
+        return fail(WT_E_INVALID, "wt_decoder_read_logprobs: null output or row stride %d < max_length %d", ld, e->max_length);
+    if (no_speech_prob && e->lp_cur.no_speech_token_id < 0)
+        return fail(WT_E_INVALID, "wt_decoder_read_logprobs: no_speech_prob was not requested (no_speech_token_id -1)");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemcpy2DAsync(token_logprobs, (size_t)ld * 4, e->lp_tok, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->B, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sum_logprob, e->lp_sum, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
+    if (no_speech_prob) HIPCHK(hipMemcpyAsync(no_speech_prob, e->lp_nsp, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
     return WT_OK;
 }
 

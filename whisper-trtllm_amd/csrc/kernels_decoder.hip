@@ -83,7 +83,10 @@ hipError_t launch_dec_embed(const int* ids, int ids_ld, const float* tok_emb, co
 // v_cvt_f32_f16 right before the packed FMAs.
 // GELU_IN: PROBE ONLY (wt_dbg_skinny_gelu_in): the consumer side of "fold the cross out-projection through LN3 into
 // fc1" -- fc2 would have to finish x = gelu((u - mean.r).rstd + t) on its own activation slice.  Timing only (statistics are stand-ins).
-template <int NB, int V, int NW, bool W_NT, bool HALF = false, bool ARGMAX = false, bool WH = false, bool GELU_IN = false>
+// LP (log-probability mode, ARGMAX only; wt_decoder_set_logprobs): 1 = every output lane also keeps the online log-sum-exp pair of its masked
+// scores, 2 = and a second pair over the raw logits (no_speech_prob); merged per workgroup through the LDS stage of the candidates, in a
+// fixed order, and written beside am_val / am_idx with one vector store.  A compile-time form: the LP = 0 instantiations are untouched.
+template <int NB, int V, int NW, bool W_NT, bool HALF = false, bool ARGMAX = false, bool WH = false, bool GELU_IN = false, int LP = 0>
 __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsplit, const int KS, const int rows_per_group,
                                             const int block) {
     extern __shared__ __attribute__((aligned(16))) float sk_smem[];
@@ -345,6 +348,8 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
                                 // epilogue would be an exposed L2 round trip per row pair: measured +10 us on the 51864-row GEMV)
     bool am_at_begin = false;
     float* am_tr = nullptr;
+    float lp_m = -INFINITY, lp_s = 0.f, lp_rm = -INFINITY, lp_rs = 0.f;   // LP: (max, sum of exp) of the masked / of the raw scores
+    static_assert(LP == 0 || ARGMAX, "the log-sum-exp pairs belong to the ARGMAX epilogue");
     if constexpr (ARGMAX) {
         am_mk[0] = p.am_mask[min(row_begin + my_r, p.N - 1)];
         am_at_begin = p.st->cur_len[min(my_b, p.B - 1)] == p.am_begin_index;
@@ -418,8 +423,16 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
             if constexpr (ARGMAX) {  // logits processors (Suppress -> SuppressAtBegin) + running argmax, logits_process.py:1281-1311
                 v *= p.q_scale;
                 if (am_tr) am_tr[n] = v;
+                if constexpr (LP == 2) {
+                    lse_add(lp_rm, lp_rs, v);
+                    if (n == p.am_ns) p.am_side[2 * my_b + 1] = v;
+                }
                 const uint8_t mk = am_mk[cur];
                 if ((mk & 1) || ((mk & 2) && am_at_begin)) v = -INFINITY;
+                if constexpr (LP != 0) {
+                    lse_add(lp_m, lp_s, v);
+                    if (n == p.am_eos) p.am_side[2 * my_b] = v;
+                }
                 if (argmax_better(v, n, am_best, am_bidx)) {
                     am_best = v;
                     am_bidx = n;
@@ -458,6 +471,18 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
             cv[(wave * 2 + my_r) * NB + my_b] = am_best;
             ci[(wave * 2 + my_r) * NB + my_b] = am_bidx;
         }
+        float* cl = sk_smem + 2 * NW * 2 * NB;               // LP: [4][NW][2][NB] = m, s, raw m, raw s
+        if constexpr (LP != 0) {
+            if (is_out_lane) {
+                const int at = (wave * 2 + my_r) * NB + my_b;
+                cl[at] = lp_m;
+                cl[NW * 2 * NB + at] = lp_s;
+                if constexpr (LP == 2) {
+                    cl[2 * NW * 2 * NB + at] = lp_rm;
+                    cl[3 * NW * 2 * NB + at] = lp_rs;
+                }
+            }
+        }
         __syncthreads();
         if (tid < p.B) {
             float best = -INFINITY;
@@ -472,6 +497,14 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
             }
             p.am_val[(size_t)tid * p.am_ld + block] = best;
             p.am_idx[(size_t)tid * p.am_ld + block] = bidx;
+            if constexpr (LP != 0) {   // the pairs of the NW x 2 output lanes of batch row `tid`, merged in slot order
+                float m = -INFINITY, s = 0.f, rm = -INFINITY, rs = 0.f;
+                for (int i = 0; i < NW * 2; ++i) {
+                    lse_merge(m, s, cl[i * NB + tid], cl[NW * 2 * NB + i * NB + tid]);
+                    if constexpr (LP == 2) lse_merge(rm, rs, cl[2 * NW * 2 * NB + i * NB + tid], cl[3 * NW * 2 * NB + i * NB + tid]);
+                }
+                p.am_lse[(size_t)tid * p.am_ld + block] = make_float4(m, s, rm, rs);
+            }
         }
     }
 }
@@ -484,6 +517,14 @@ template <int NB, int V, int NW, bool W_NT, bool ARGMAX = false, bool WH = false
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_gemm_kernel(const SkinnyParams p, const int nsplit, const int KS,
                                                                              const int rows_per_group) {
     skinny_body<NB, V, NW, W_NT, false, ARGMAX, WH>(p, nsplit, KS, rows_per_group, blockIdx.x);
+}
+// the vocabulary GEMV of the log-probability mode: the ARGMAX epilogue with the log-sum-exp pairs (LP = 1) and the raw pair (LP = 2)
+// (one block per SIMD set: the pairs push the 8-row form past 256 registers, and the vocabulary GEMV's plan is one block per CU anyway --
+//  with two the compiler spilled 8-16 bytes per lane to scratch, a vector-memory access queued behind the weight loads)
+template <int NB, int V, int NW, bool W_NT, bool WH, int LP>
+__global__ __launch_bounds__(64 * NW, 1) void skinny_logprob_kernel(const SkinnyParams p, const int nsplit, const int KS,
+                                                                                const int rows_per_group) {
+    skinny_body<NB, V, NW, W_NT, false, true, WH, false, LP>(p, nsplit, KS, rows_per_group, blockIdx.x);
 }
 
 // probe (see GELU_IN above): the K > 1024 direct-activation GEMV with the GELU / LayerNorm finish in its prologue
@@ -556,11 +597,47 @@ static hipError_t skinny_smem_attr() {
 }
 
 template <int NB, int V, int NW>
+static hipError_t skinny_logprob_launch(const SkinnyParams& p, const SkinnyPlan& pl, hipStream_t s) {
+    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
+    static_assert(6 * NW * 2 * NB <= NB * 1024, "candidates + four pair arrays fit the activation staging area");
+    static PerDeviceFlag attr_set;
+    if (!attr_set.get() && smem > 48 * 1024) {
+        for (const void* f : {reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, false, 1>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, true, 1>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, false, 1>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, true, 1>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, false, 2>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, true, 2>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, false, 2>),
+                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, true, 2>)}) {
+            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+            if (e != hipSuccess) return e;
+        }
+        attr_set.set();
+    }
+#define WT_SK_LP(NT_, WH_, LP_) \
+    hipLaunchKernelGGL((skinny_logprob_kernel<NB, V, NW, NT_, WH_, LP_>), dim3(pl.grid), dim3(64 * NW), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group)
+    switch ((p.am_lp == 2 ? 4 : 0) | (p.w_nt ? 2 : 0) | (p.w_half ? 1 : 0)) {
+    case 0: WT_SK_LP(false, false, 1); break;
+    case 1: WT_SK_LP(false, true, 1); break;
+    case 2: WT_SK_LP(true, false, 1); break;
+    case 3: WT_SK_LP(true, true, 1); break;
+    case 4: WT_SK_LP(false, false, 2); break;
+    case 5: WT_SK_LP(false, true, 2); break;
+    case 6: WT_SK_LP(true, false, 2); break;
+    default: WT_SK_LP(true, true, 2); break;
+    }
+#undef WT_SK_LP
+    return hipGetLastError();
+}
+
+template <int NB, int V, int NW>
 static hipError_t skinny_launch_cfg(const SkinnyParams& p, hipStream_t s) {
     SkinnyPlan pl;
     hipError_t e = skinny_plan<NB, V, NW>(p, &pl);
     if (e == hipSuccess) e = skinny_smem_attr<NB, V, NW>();
     if (e != hipSuccess) return e;
+    if (p.ymode == YMODE_ARGMAX && p.am_lp) return skinny_logprob_launch<NB, V, NW>(p, pl, s);
     constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
 #define WT_SK_LAUNCH(NT_, AM_, WH_) \
     hipLaunchKernelGGL((skinny_gemm_kernel<NB, V, NW, NT_, AM_, WH_>), dim3(pl.grid), dim3(64 * NW), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group)
@@ -629,6 +706,9 @@ hipError_t launch_skinny(const SkinnyParams& p, hipStream_t s) {
     if (p.B < 1 || p.B > 16 || (p.K & 3)) return hipErrorInvalidValue;
     if (p.parts && p.X2) return hipErrorInvalidValue;   // half-staged: pair launches only
     if (p.ymode == YMODE_ARGMAX && (!p.am_mask || !p.am_val || !p.am_idx || p.am_ld < skinny_grid(p) || p.resid || p.act)) return hipErrorInvalidValue;
+    if (p.am_lp && (p.ymode != YMODE_ARGMAX || (p.am_lp != 1 && p.am_lp != 2) || !p.am_lse || !p.am_side || p.am_eos < 0 || p.am_eos >= p.N ||
+                    (p.am_lp == 2 && (p.am_ns < 0 || p.am_ns >= p.N))))
+        return hipErrorInvalidValue;
     if (p.B <= 2) return skinny_launch_cfg<2, 4, 4>(p, s);
     if (p.B <= 4) return skinny_launch_cfg<4, 4, 4>(p, s);
     if (p.B <= 8) return skinny_launch_cfg<8, 4, 4>(p, s);
@@ -1101,9 +1181,13 @@ hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s) {
 //   greedy_select_kernel  grid (SELECT_CHUNKS, B): masked partial argmax of one vocabulary chunk (lowest index on ties);
 //   greedy_finish_kernel  one block: final argmax per row, forced / pad / EOS rules, append, advance the step counters,
 //                         stop test, and the NEXT step's input embedding (embed_tokens[tok] + embed_positions[pos]).
+// LP (log-probability mode): the chunk's log-sum-exp pairs beside its candidate -- the same quantities as the LP epilogue of the
+// vocabulary GEMV, so the fused and the non-fused step feed one finish kernel.
+template <bool LP = false>
 __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p) {
     __shared__ float s_val[4];
     __shared__ int s_idx[4];
+    __shared__ float4 s_lse[4];
     const DecState* st = p.st;
     if (st->done) return;  // steps enqueued past the stop test are no-ops
     const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
@@ -1112,8 +1196,19 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
     float* tr = p.trace ? p.trace + ((size_t)b * (p.max_length - 1) + step) * p.V : nullptr;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
+    float lm = -INFINITY, ls = 0.f, rm = -INFINITY, rs = 0.f;
     auto consider = [&](float x, uint8_t mk, int v) {
+        if constexpr (LP) {
+            if (p.lp_ns >= 0) {
+                lse_add(rm, rs, x);
+                if (v == p.lp_ns) p.lp_side[2 * b + 1] = x;
+            }
+        }
         if ((mk & 1) || ((mk & 2) && at_begin)) x = -INFINITY;
+        if constexpr (LP) {
+            lse_add(lm, ls, x);
+            if (v == p.eos) p.lp_side[2 * b] = x;
+        }
         if (argmax_better(x, v, best, bidx)) {
             best = x;
             bidx = v;
@@ -1152,10 +1247,15 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
             best = ov;
             bidx = oi;
         }
+        if constexpr (LP) {
+            lse_merge(lm, ls, __shfl_xor(lm, o), __shfl_xor(ls, o));
+            lse_merge(rm, rs, __shfl_xor(rm, o), __shfl_xor(rs, o));
+        }
     }
     if ((tid & 63) == 0) {
         s_val[tid >> 6] = best;
         s_idx[tid >> 6] = bidx;
+        if constexpr (LP) s_lse[tid >> 6] = make_float4(lm, ls, rm, rs);
     }
     __syncthreads();
     if (tid == 0) {
@@ -1166,6 +1266,13 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
             }
         p.part_val[b * SELECT_CHUNKS + chunk] = best;
         p.part_idx[b * SELECT_CHUNKS + chunk] = bidx;
+        if constexpr (LP) {
+            for (int i = 1; i < 4; ++i) {
+                lse_merge(lm, ls, s_lse[i].x, s_lse[i].y);
+                lse_merge(rm, rs, s_lse[i].z, s_lse[i].w);
+            }
+            p.lp_part[b * SELECT_CHUNKS + chunk] = make_float4(lm, ls, rm, rs);
+        }
     }
 }
 
@@ -1176,8 +1283,11 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
 // (sum, max) pairs: s * exp(m - nm) with the empty pair (0, -inf) contributing 0 and a NaN sum staying NaN.
 __device__ __forceinline__ float ts_rescale(float s, float m, float nm) { return s == 0.f ? 0.f : s * expf(m - nm); }
 
+// LP (log-probability mode): TsPart also carries the text-side pair (xmax, xsum), and lp_part the raw pair of the chunk (no_speech_prob).
+template <bool LP = false>
 __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
     __shared__ TsPart s_part[4];
+    __shared__ float2 s_raw[4];
     const DecState* st = p.st;
     if (st->done) return;  // steps enqueued past the stop test are no-ops
     const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
@@ -1198,13 +1308,26 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
     r.tmax = r.smax = r.zmax = -INFINITY;
     r.targ = r.sarg = 0x7fffffff;
     r.zsum = 0.f;
+    r.xmax = -INFINITY;
+    r.xsum = 0.f;
+    float rm = -INFINITY, rs = 0.f;
     auto consider = [&](float x, uint8_t mk, int v) {
+        if constexpr (LP) {
+            if (p.lp_ns >= 0) {
+                lse_add(rm, rs, x);
+                if (v == p.lp_ns) p.lp_side[2 * b + 1] = x;
+            }
+        }
         if ((mk & 1) || ((mk & 2) && at_begin) || v == p.no_ts || v < text_lo || v > ts_hi) x = -INFINITY;
+        if constexpr (LP) {
+            if (v == p.eos) p.lp_side[2 * b] = x;
+        }
         if (v < p.tb) {
             if (argmax_better(x, v, r.tmax, r.targ)) {
                 r.tmax = x;
                 r.targ = v;
             }
+            if constexpr (LP) lse_add(r.xmax, r.xsum, x);
         } else {
             if (argmax_better(x, v, r.smax, r.sarg)) {
                 r.smax = x;
@@ -1255,6 +1378,7 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
         const float nm = fmaxf(a.zmax, o.zmax);   // (never NaN: zmax only takes finite or infinite scores)
         a.zsum = ts_rescale(a.zsum, a.zmax, nm) + ts_rescale(o.zsum, o.zmax, nm);
         a.zmax = nm;
+        if constexpr (LP) lse_merge(a.xmax, a.xsum, o.xmax, o.xsum);
     };
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -1265,13 +1389,25 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
         x.sarg = __shfl_xor(r.sarg, o);
         x.zmax = __shfl_xor(r.zmax, o);
         x.zsum = __shfl_xor(r.zsum, o);
+        if constexpr (LP) {
+            x.xmax = __shfl_xor(r.xmax, o);
+            x.xsum = __shfl_xor(r.xsum, o);
+            lse_merge(rm, rs, __shfl_xor(rm, o), __shfl_xor(rs, o));
+        }
         merge(r, x);
     }
-    if ((tid & 63) == 0) s_part[tid >> 6] = r;
+    if ((tid & 63) == 0) {
+        s_part[tid >> 6] = r;
+        if constexpr (LP) s_raw[tid >> 6] = make_float2(rm, rs);
+    }
     __syncthreads();
     if (tid == 0) {
         for (int i = 1; i < 4; ++i) merge(r, s_part[i]);
         p.ts_part[b * SELECT_CHUNKS + chunk] = r;
+        if constexpr (LP) {
+            for (int i = 1; i < 4; ++i) lse_merge(rm, rs, s_raw[i].x, s_raw[i].y);
+            p.lp_part[b * SELECT_CHUNKS + chunk] = make_float4(-INFINITY, 0.f, rm, rs);
+        }
     }
 }
 
@@ -1280,12 +1416,24 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
 __device__ __forceinline__ void ts_request(const SelectParams& p, const int b, const int l, TsPart& c) {
     c = p.ts_part[(size_t)min(b, p.B - 1) * SELECT_CHUNKS + min(l, SELECT_CHUNKS - 1)];
 }
+// log-probability mode: what the finish kernel needs of a row's pick -- the score of the chosen token, the log-sum-exp pair (m, s) of the
+// scores it competed with, whether its step is a forced one (one survivor: log-probability 0) and whether rule 5 masked the text ids
+struct LpPick {
+    float num, m, s;
+    bool forced, text_masked;
+};
 // rules 2 and 5 and the argmax of one row; every lane of the group returns the same token
-__device__ __forceinline__ int ts_pick(const SelectParams& p, const int b, const int l, const int lpb, const TsPart& c, const int cur_len) {
+template <bool LP = false>
+__device__ __forceinline__ int ts_pick(const SelectParams& p, const int b, const int l, const int lpb, const TsPart& c, const int cur_len,
+                                       LpPick* lp = nullptr) {
     float tm = -INFINITY, sm = -INFINITY, zm = -INFINITY, zs = 0.f;
     int ti = 0x7fffffff, si = 0x7fffffff;
+    float xm = -INFINITY, xs = 0.f;
     if (b < p.B && l < SELECT_CHUNKS) {
         tm = c.tmax; ti = c.targ; sm = c.smax; si = c.sarg; zm = c.zmax; zs = c.zsum;
+        if constexpr (LP) {
+            xm = c.xmax; xs = c.xsum;
+        }
     }
     float M = zm;
     for (int o = lpb >> 1; o >= 1; o >>= 1) {   // lpb <= 64 and a power of two: a group never straddles a wave
@@ -1308,6 +1456,18 @@ __device__ __forceinline__ int ts_pick(const SelectParams& p, const int b, const
     if (cur_len == p.ts_begin_index - 1) tok = p.tb;        // rule 2: <|0.00|> opens the transcript
     else if (lse > tm) tok = si;                            // rule 5: the timestamps' total mass beats every text token
     else tok = argmax_better(sm, si, tm, ti) ? si : ti;
+    if constexpr (LP) {   // rule 5 leaves the timestamps alone in the softmax; otherwise text and timestamps share it
+        for (int o = lpb >> 1; o >= 1; o >>= 1) lse_merge(xm, xs, __shfl_xor(xm, o), __shfl_xor(xs, o));
+        lp->forced = cur_len == p.ts_begin_index - 1;
+        lp->text_masked = !lp->forced && lse > tm;
+        lp->m = M;
+        lp->s = Z;
+        lp->num = sm;
+        if (!lp->text_masked) {
+            lse_merge(lp->m, lp->s, xm, xs);
+            lp->num = argmax_better(sm, si, tm, ti) ? sm : tm;
+        }
+    }
     if ((unsigned)tok >= (unsigned)p.V) tok = p.eos;        // unreachable with a NaN-aware argmax; never index the embedding out of range
     if (b < p.B && l == 0) {
         if (p.ts_tok) p.ts_tok[b] = tok;
@@ -1337,7 +1497,25 @@ __device__ __forceinline__ void finish_request(const SelectParams& p, const int 
         c.pi[k] = p.part_idx[pbase + i];
     }
 }
-__device__ __forceinline__ int finish_argmax(const SelectParams& p, const int b, const int l, const int lpb, const FinishCand& c) {
+// a row's log-sum-exp pairs over its n_parts partials (log-probability mode): lane l merges partials l, l + lpb, .. in that order, then the
+// group's lanes merge by a butterfly -- a fixed order, so the result is bitwise repeatable; every lane of the group ends with the same pairs
+__device__ __forceinline__ float4 finish_lse(const SelectParams& p, const int b, const int l, const int lpb) {
+    const size_t pbase = (size_t)min(b, p.B - 1) * p.n_parts;
+    float m = -INFINITY, s = 0.f, rm = -INFINITY, rs = 0.f;
+    for (int i = l; i < p.n_parts; i += lpb) {
+        const float4 v = p.lp_part[pbase + i];
+        lse_merge(m, s, v.x, v.y);
+        lse_merge(rm, rs, v.z, v.w);
+    }
+    for (int o = lpb >> 1; o >= 1; o >>= 1) {
+        lse_merge(m, s, __shfl_xor(m, o), __shfl_xor(s, o));
+        lse_merge(rm, rs, __shfl_xor(rm, o), __shfl_xor(rs, o));
+    }
+    return make_float4(m, s, rm, rs);
+}
+template <bool LP = false>
+__device__ __forceinline__ int finish_argmax(const SelectParams& p, const int b, const int l, const int lpb, const FinishCand& c,
+                                             float* best_out = nullptr) {
     const size_t pbase = (size_t)min(b, p.B - 1) * p.n_parts;
     float best = -INFINITY;
     int bidx = 0x7fffffff;
@@ -1365,6 +1543,7 @@ __device__ __forceinline__ int finish_argmax(const SelectParams& p, const int b,
             bidx = oi;
         }
     }
+    if constexpr (LP) *best_out = best;
     if ((unsigned)bidx >= (unsigned)p.V) bidx = p.eos;   // unreachable with a NaN-aware argmax; never index the embedding out of range
     return bidx;
 }
@@ -1380,7 +1559,10 @@ __device__ __forceinline__ void finish_embed(const SelectParams& p, const int* s
 }
 
 // TS: the timestamp mode's pick (ts_pick over ts_select_kernel's partials) instead of the plain argmax; the bookkeeping is shared
-template <bool TS>
+// LP: the log-probability mode -- token_logprob[b][cur_len] = s[tok] - logsumexp(s) over the step's processed scores s (0 at a forced
+// position; the EOS score where a bench switch replaced the token), its running sum while the row is unfinished, and at step 0
+// no_speech_prob = softmax(raw logits)[lp_ns].  The LP = false instantiations are the kernels as they were.
+template <bool TS, bool LP = false>
 __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p) {
     __shared__ int s_tok[MAX_ROWS];
     __shared__ int s_pos[MAX_ROWS];
@@ -1409,12 +1591,40 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     const int forced = p.forced[cur_len];                          // ForceTokensLogitsProcessor
     const int row_eos = p.force_eos_rows ? p.force_eos_rows[bc] : -1;
     int tok;
-    if constexpr (TS) tok = ts_pick(p, b, l, lpb, tcand, st->cur_len[bc]);
-    else tok = finish_argmax(p, b, l, lpb, cand);
+    LpPick pick;
+    float4 lse4;
+    if constexpr (LP) lse4 = finish_lse(p, b, l, lpb);
+    if constexpr (TS) {
+        if constexpr (LP) tok = ts_pick<true>(p, b, l, lpb, tcand, st->cur_len[bc], &pick);
+        else tok = ts_pick(p, b, l, lpb, tcand, st->cur_len[bc]);
+    } else {
+        if constexpr (LP) {
+            tok = finish_argmax<true>(p, b, l, lpb, cand, &pick.num);
+            pick.m = lse4.x; pick.s = lse4.y; pick.forced = false; pick.text_masked = false;
+        } else {
+            tok = finish_argmax(p, b, l, lpb, cand);
+        }
+    }
     if (b < p.B && l == 0) {
         if (forced >= 0) tok = forced;
         if (p.force_eos_step >= 0 && step == p.force_eos_step) tok = p.eos;  // bench-only transcript length
         if (row_eos >= 0 && step == row_eos) tok = p.eos;                    // ... per row (variable-length workload)
+        if constexpr (LP) {
+            if (unf) {
+                float lpv;
+                if (forced >= 0 || pick.forced) {   // one survivor at 0, the rest -inf (a bench switch may still have replaced it)
+                    lpv = tok == (forced >= 0 ? forced : p.tb) ? 0.f : -INFINITY;
+                } else {
+                    float num = pick.num;
+                    if ((p.force_eos_step >= 0 && step == p.force_eos_step) || (row_eos >= 0 && step == row_eos))
+                        num = pick.text_masked && p.eos < p.tb ? -INFINITY : p.lp_side[2 * b];   // the switches replace the token, not the scores
+                    lpv = (num - pick.m) - logf(pick.s);
+                }
+                p.lp_tok[(size_t)b * p.max_length + cur_len] = lpv;
+                p.lp_sum[b] += lpv;
+            }
+            if (p.lp_ns >= 0 && step == 0) p.lp_nsp[b] = expf(p.lp_side[2 * b + 1] - lse4.z) / lse4.w;
+        }
         if (!unf) tok = p.pad;                                 // finished rows keep emitting pad
         p.ids[(size_t)b * p.max_length + cur_len] = tok;
         if (tok == p.eos) p.unfinished[b] = 0;
@@ -2021,6 +2231,8 @@ hipError_t launch_beam_finalize(const SelectParams& p, hipStream_t s) {
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     if (p.B > MAX_ROWS || p.n_parts < 1 || (!p.fused && p.n_parts != SELECT_CHUNKS)) return hipErrorInvalidValue;
     if (p.stream && (!p.host_ids || !p.host_len || p.trace)) return hipErrorInvalidValue;
+    if (p.lp_on && (p.beam_on || !p.lp_part || !p.lp_side || !p.lp_tok || !p.lp_sum || p.lp_ns >= p.V || (p.lp_ns >= 0 && !p.lp_nsp)))
+        return hipErrorInvalidValue;
     if (p.beam_on) {   // beam search: batch decodes only, over logits in HBM
         if (!beam_params_ok(p)) return hipErrorInvalidValue;
         hipLaunchKernelGGL(beam_select_kernel, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
@@ -2030,11 +2242,22 @@ hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     if (p.ts_on) {   // timestamp mode: batch decodes only, over logits in HBM
         if (p.fused || p.stream || !p.ts_part || p.tb <= 0 || p.tb >= p.V || p.no_ts < 0 || p.no_ts >= p.tb || p.ts_begin_index < 2)
             return hipErrorInvalidValue;
-        hipLaunchKernelGGL(ts_select_kernel, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(greedy_finish_kernel<true>, dim3(1), dim3(256), 0, s, p);
+        if (p.lp_on) {
+            hipLaunchKernelGGL(ts_select_kernel<true>, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((greedy_finish_kernel<true, true>), dim3(1), dim3(256), 0, s, p);
+        } else {
+            hipLaunchKernelGGL(ts_select_kernel<false>, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
+            hipLaunchKernelGGL(greedy_finish_kernel<true>, dim3(1), dim3(256), 0, s, p);
+        }
         return hipGetLastError();
     }
-    if (!p.fused) hipLaunchKernelGGL(greedy_select_kernel, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);  // else: done by the vocabulary GEMV
+    if (p.lp_on) {   // log-probability mode: batch decodes only; the same launch count as the plain tail
+        if (p.stream) return hipErrorInvalidValue;
+        if (!p.fused) hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
+        hipLaunchKernelGGL((greedy_finish_kernel<false, true>), dim3(1), dim3(256), 0, s, p);
+        return hipGetLastError();
+    }
+    if (!p.fused) hipLaunchKernelGGL(greedy_select_kernel<false>, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);  // else: done by the vocabulary GEMV
     if (p.stream) hipLaunchKernelGGL(stream_finish_kernel, dim3(1), dim3(256), 0, s, p);
     else hipLaunchKernelGGL(greedy_finish_kernel<false>, dim3(1), dim3(256), 0, s, p);
     return hipGetLastError();

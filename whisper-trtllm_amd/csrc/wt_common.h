@@ -106,6 +106,13 @@ struct SkinnyParams {
     int* am_idx;
     float* am_trace;       // optional raw-logits trace [B][am_trace_steps][N] (row st->step), or nullptr
     int am_ld, am_begin_index, am_trace_steps;
+    // log-probability mode (am_lp != 0; wt_decoder_set_logprobs): the LP instantiations of the ARGMAX epilogue also reduce, per batch row and
+    // workgroup, the online log-sum-exp pair (max, sum of exp(x - max)) of the masked scores -- and, with am_lp == 2, a second pair over the
+    // raw logits (no_speech_prob) -- into am_lse [B][am_ld] as (m, s, raw m, raw s); the masked score of id am_eos and the raw logit of id
+    // am_ns (< 0: none) go to am_side [B][2].  am_lp == 0: the plain instantiations run, exactly as before.
+    float4* am_lse;
+    float* am_side;
+    int am_lp, am_eos, am_ns;
 };
 
 // ---- decode attention (query length 1), split over the key axis ---------------------------------------------
@@ -277,7 +284,7 @@ struct TsPart {
     float smax;
     int sarg;
     float zmax, zsum;
-    int pad[2];
+    float xmax, xsum;      // log-probability mode only (else unused): the same pair over the chunk's text scores
 };
 
 // Beam search (wt_decoder_set_beam_search): rows are [utterance][beam], row = u * nb + j.
@@ -351,7 +358,34 @@ struct SelectParams {
     // beam search (beam_on != 0; wt_decoder_set_beam_search): plain logits in HBM, then beam_select_kernel + beam_finish_kernel
     int beam_on;
     BeamParams beam;
+    // log-probability mode (lp_on != 0; wt_decoder_set_logprobs): the LP instantiations of the select / finish kernels run.  lp_part
+    // [B][n_parts] holds one (m, s, raw m, raw s) per partial (the vocabulary GEMV's workgroups, or the select kernels' chunks), lp_side
+    // [B][2] the masked score of the EOS id and the raw logit of id lp_ns.  The finish kernel writes token_logprob[b][cur_len] into lp_tok
+    // [B][max_length], adds it to lp_sum [B] while row b is unfinished, and at step 0 stores softmax(raw logits)[lp_ns] into lp_nsp [B]
+    // (lp_ns < 0: off).
+    int lp_on, lp_ns;
+    float4* lp_part;
+    float* lp_side;
+    float* lp_tok;
+    float* lp_sum;
+    float* lp_nsp;
 };
+// online log-sum-exp pairs (m = largest score that is neither NaN nor -inf, s = sum of exp(x - m)): the empty pair is (-inf, 0), a NaN score
+// makes s NaN
+__device__ __forceinline__ float lse_rescale(float s, float m, float nm) { return s == 0.f ? 0.f : s * expf(m - nm); }
+__device__ __forceinline__ void lse_add(float& m, float& s, const float x) {
+    if (x > m) {
+        s = lse_rescale(s, m, x) + 1.f;
+        m = x;
+    } else if (x != -INFINITY) {
+        s += expf(x - m);
+    }
+}
+__device__ __forceinline__ void lse_merge(float& m, float& s, const float om, const float os) {   // (m, s) += (om, os), in this order
+    const float nm = fmaxf(m, om);
+    s = lse_rescale(s, m, nm) + lse_rescale(os, om, nm);
+    m = nm;
+}
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s);
 hipError_t launch_beam_init(const SelectParams& p, hipStream_t s);       // beam scores 0 / -1e9, identity ancestry, empty hypothesis stores
 hipError_t launch_beam_finalize(const SelectParams& p, hipStream_t s);   // BeamSearchScorer.finalize into beam.out_ids / out_scores (idempotent)
@@ -398,6 +432,9 @@ inline SkinnyParams vocab_skinny_params(const float* h, const float* ln_w, const
 inline int vocab_skinny_fuse_argmax(SkinnyParams& k, const SelectParams& sp) {
     k.ymode = YMODE_ARGMAX; k.Y = nullptr; k.am_mask = sp.mask; k.am_val = sp.part_val; k.am_idx = sp.part_idx;
     k.am_begin_index = sp.begin_index; k.am_trace = sp.trace; k.am_trace_steps = sp.max_length - 1;
+    if (sp.lp_on) {
+        k.am_lp = sp.lp_ns >= 0 ? 2 : 1; k.am_lse = sp.lp_part; k.am_side = sp.lp_side; k.am_eos = sp.eos; k.am_ns = sp.lp_ns;
+    }
     const int grid = skinny_grid(k);
     k.am_ld = grid;
     return grid;

@@ -219,6 +219,35 @@ def _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step,
         raise ValueError("beam search does not take logits_trace / force_eos_step(s)")
 
 
+class DecodeScores:
+    """Confidence signals of a greedy decode (generate(..., return_logprobs=True)), openai-whisper's definitions:
+    `token_logprobs` float32 [B, len]: log-probability of every emitted token under the step's processed scores (0 at position 0, at
+    forced positions and behind a row's EOS); `sum_logprob` float32 [B]: the row's sum through its EOS; `avg_logprob` float32 [B] =
+    sum_logprob / scored positions (generated tokens including the EOS and forced ones; a row without EOS: all len - 1 of them);
+    `no_speech_prob` float32 [B] or None: softmax(raw logits of the first step)[no_speech_token_id]."""
+
+    def __init__(self, ids, token_logprobs, sum_logprob, no_speech_prob, eos_token_id: int):
+        import torch
+        self.token_logprobs, self.sum_logprob, self.no_speech_prob = token_logprobs, sum_logprob, no_speech_prob
+        body = ids[:, 1:]
+        is_eos = body == eos_token_id
+        width = torch.full((body.shape[0],), body.shape[1], dtype=torch.int64, device=body.device)
+        self.n_scored = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, width)
+        self.avg_logprob = sum_logprob / self.n_scored.clamp(min=1).to(sum_logprob.dtype)
+
+
+def _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, vocab_size):
+    """What the engine refuses (wt_decoder_begin: WT_E_UNSUPPORTED, wt_decoder_set_logprobs: WT_E_INVALID), refused before anything is enqueued."""
+    if not return_logprobs:
+        if no_speech_token_id is not None:
+            raise ValueError("no_speech_token_id needs return_logprobs=True")
+        return
+    if num_beams > 1:
+        raise ValueError("beam search and return_logprobs cannot be combined (return_scores gives the beams' sequence score)")
+    if no_speech_token_id is not None and not (isinstance(no_speech_token_id, int) and 0 <= no_speech_token_id < vocab_size):
+        raise ValueError(f"no_speech_token_id must be an id in [0, {vocab_size}), got {no_speech_token_id!r}")
+
+
 def _check_token_timestamp_args(config, info, return_token_timestamps, alignment_heads, median_filter_width, num_beams):
     """Token-level timestamps: the head list to use ([] when the mode is off).  `alignment_heads` of the call wins over the config's
     (generation_config.json's `alignment_heads`, which examples/whisper/_common.py copies into the config).  Refused before anything is
@@ -317,6 +346,26 @@ class WhisperDecoderEngine:
                    "wt_decoder_set_token_timestamps")
         self._tt_heads = list(heads)
 
+    def _set_logprobs(self, on: bool = False, no_speech_token_id=None):
+        t = _lib.LogprobParams(1, -1 if no_speech_token_id is None else int(no_speech_token_id)) if on else None
+        _lib.check(self.session._lib.wt_decoder_set_logprobs(self.session.handle, ctypes.byref(t) if t is not None else None),
+                   "wt_decoder_set_logprobs")
+        self._lp_ns = no_speech_token_id if on else None
+
+    def read_logprobs(self, ids):
+        """DecodeScores of the decode in flight for its ids [B, cur_len] (wt_decoder_read_logprobs, stream-ordered)."""
+        import torch
+        ml = self._p.max_length
+        dev = self._enc.device
+        tok = torch.empty(self._B, ml, dtype=torch.float32, device=dev)
+        total = torch.empty(self._B, dtype=torch.float32, device=dev)
+        nsp = torch.empty(self._B, dtype=torch.float32, device=dev) if self._lp_ns is not None else None
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_decoder_read_logprobs(self.session.handle, tok.data_ptr(), ml, total.data_ptr(),
+                                                               nsp.data_ptr() if nsp is not None else None, ctypes.c_void_p(stream)),
+                   "wt_decoder_read_logprobs")
+        return DecodeScores(ids, tok[:, :ids.shape[1]].clone(), total, nsp, self._p.eos_token_id)
+
     def read_token_timestamps(self, cur_len: int):
         """Token-level timestamps of the decode in flight (wt_decoder_read_token_timestamps: the cross-attention DTW post-pass on the
         device, stream-ordered): float32 [B, cur_len] seconds on the GPU, entry 0 of a row is 0."""
@@ -355,8 +404,9 @@ class WhisperDecoderEngine:
 
     def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
               return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
-              return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7):
-        """Start a decode (wt_decoder_begin).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
+              return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7,
+              return_logprobs: bool = False, no_speech_token_id=None):
+        """Start a decode (wt_decoder_begin).  `return_logprobs` / `no_speech_token_id`: see `generate` (read with `read_logprobs`).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
         the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
         `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
         (False or True); utterances x num_beams <= 16 rows per call; not together with timestamps, logits_trace or force_eos_step(s).
@@ -367,6 +417,7 @@ class WhisperDecoderEngine:
         _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps)
         i = self.session.info
         tt_heads = _check_token_timestamp_args(self.config, i, True, alignment_heads, median_filter_width, num_beams) if return_token_timestamps else []
+        _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, i.vocab_size)
         if encoder_hidden.dtype != torch.float32 or tuple(encoder_hidden.shape[1:]) != (i.max_source_positions, i.d_model):
             raise ValueError(f"encoder_hidden must be float32 [B,{i.max_source_positions},{i.d_model}]")
         if not encoder_hidden.is_cuda or (logits_trace is not None and not logits_trace.is_cuda):
@@ -380,6 +431,7 @@ class WhisperDecoderEngine:
         self._set_timestamp_rules(return_timestamps)
         self._set_beam_search(num_beams, length_penalty, early_stopping)
         self._set_token_timestamps(tt_heads, median_filter_width)
+        self._set_logprobs(return_logprobs, no_speech_token_id)
         self._beams = int(num_beams) if num_beams > 1 else 1
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.session._lib.wt_decoder_begin(self.session.handle, self._enc.data_ptr(), self._B, ctypes.byref(self._p),
@@ -444,8 +496,11 @@ class WhisperDecoderEngine:
     def generate(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, chunk: int = 0, force_eos_steps=None,
                  lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, return_scores: bool = False, return_token_timestamps: bool = False, alignment_heads=None,
-                 median_filter_width: int = 7):
+                 median_filter_width: int = 7, return_logprobs: bool = False, no_speech_token_id=None):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
+        `return_logprobs`: token log-probabilities from the device (wt_decoder_set_logprobs, no extra launch): returns (ids, DecodeScores),
+        or (ids, token timestamps, DecodeScores) with `return_token_timestamps`; `no_speech_token_id` also fills
+        DecodeScores.no_speech_prob.  Greedy decoding only (not with num_beams > 1).
         `return_timestamps`: timestamp mode (see `begin`).  `num_beams` > 1: beam search (see `begin`), the best hypothesis per
         utterance; `return_scores`: (ids, float32 sequence scores [B]) -- beam search only.
 
@@ -453,6 +508,8 @@ class WhisperDecoderEngine:
         enqueued past the stop.  `chunk` > 0 selects the older protocol -- `chunk` steps between two synchronising polls.
         `return_token_timestamps`: returns (ids, float32 token timestamps [B, len] in seconds) -- see `begin`."""
         _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step, force_eos_steps)
+        if return_logprobs or no_speech_token_id is not None:
+            _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, self.session.info.vocab_size)
         if return_scores and num_beams <= 1:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence score)")
         tt = None
@@ -484,16 +541,25 @@ class WhisperDecoderEngine:
             import torch
             if logits_trace is not None:
                 raise ValueError(f"logits_trace supports at most {self.max_batch} utterances per call")
+            lp = {"return_logprobs": True, "no_speech_token_id": no_speech_token_id} if return_logprobs else {}
             parts = [self.generate(encoder_hidden[i:i + self.max_batch], max_length, force_eos_step, None, chunk,
                                    None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead,
-                                   return_timestamps, **(tt or {}))
+                                   return_timestamps, **(tt or {}), **lp)
                      for i in range(0, encoder_hidden.shape[0], self.max_batch)]
             pad = self.config["pad_token_id"]
             cat = lambda ps, value: torch.cat([torch.nn.functional.pad(p, (0, max(q.shape[1] for q in ps) - p.shape[1]), value=value) for p in ps], dim=0)
+            if return_logprobs:   # rows are independent: the scores of the engine batches, side by side
+                ids = cat([p[0] for p in parts], pad)
+                sc = [p[-1] for p in parts]
+                scores = DecodeScores(ids, cat([x.token_logprobs for x in sc], 0.0), torch.cat([x.sum_logprob for x in sc]),
+                                      torch.cat([x.no_speech_prob for x in sc]) if no_speech_token_id is not None else None,
+                                      self.config["eos_token_id"])
+                return (ids, cat([p[1] for p in parts], 0.0), scores) if tt else (ids, scores)
             if tt:      # every engine batch ran to its own length: its rows' times are those of that length
                 return cat([p[0] for p in parts], pad), cat([p[1] for p in parts], 0.0)
             return cat(parts, pad)
-        self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, **(tt or {}))
+        self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, **(tt or {}),
+                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id)
         if chunk <= 0:
             cur, _nu = self.run(lookahead)
         else:
@@ -502,6 +568,10 @@ class WhisperDecoderEngine:
             while not done and cur < ml:
                 self.steps(min(chunk, ml - cur))
                 cur, _nu, done = self.poll()
+        if return_logprobs:
+            ids = self.read_ids(cur)
+            scores = self.read_logprobs(ids)
+            return (ids, self.read_token_timestamps(cur), scores) if tt else (ids, scores)
         return (self.read_ids(cur), self.read_token_timestamps(cur)) if tt else self.read_ids(cur)
 
     def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1,

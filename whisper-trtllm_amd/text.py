@@ -196,6 +196,14 @@ class WhisperTokenDecoder:
         return [self.decode(ids, skip_special_tokens) for ids in batch]
 
 
+def compression_ratio(text: str) -> float:
+    """openai-whisper's compression ratio of a transcript: len(utf-8 bytes) / len(zlib.compress(utf-8 bytes)).  Repetitive
+    (hallucinated) text compresses well; whisper's fallback loop rejects a segment above 2.4."""
+    import zlib
+    data = text.encode("utf-8")
+    return len(data) / len(zlib.compress(data))
+
+
 def basic_normalize(text: str) -> str:
     """Lower-case, drop bracketed/parenthesised spans, turn symbols and punctuation into spaces, collapse whitespace
     (the behaviour of the bundled BasicTextNormalizer, english_normalizer.py:75-91, plus a final strip; the full English
