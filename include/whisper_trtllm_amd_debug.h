@@ -144,6 +144,33 @@ int wt_dbg_decode_attention_rows(const float* q, const void* kcache, const void*
  * block per (split, head, u) carrying all of them; group 2 or 4 */
 int wt_dbg_decode_attention_grouped(const float* q, const void* kcache, const void* vcache, float* part, int* cnt, float* out, int B, int H,
                                     int s_cap, int len, int n_split, int group, int kv_half, void* stream);
+/* Decode attention launched as the step graph launches it (engine.hip, enqueue_layer_part): with `self_len` it reproduces LP_SELF_ATTN --
+ * fixed_len = 0, every row's key count read on the device as DecState.self_len[b] + 1 (a batch decode: all rows equal; the continuous
+ * mode: every slot at its own position) --, with `fixed_len` > 0 and ln_h / ln_r / ln_t it reproduces LP_CROSS_ATTN (folded query, all
+ * rows over fixed_len keys).  Exactly one of the two is given.
+ * self_len: HOST int32 [B], 0 <= self_len[b] < s_cap, uploaded into a DecState in `scratch`
+ *   (wt_dbg_decode_attention_state_scratch_bytes() bytes; the call then synchronises `stream`), or NULL.
+ * alive: device int32 [B] or NULL: the skip-finished-rows graph (rows with alive[b] == 0 leave before they stream K/V; the launch table
+ *   has that form for nt = 1 only, with nt = 0 the plain kernel runs and attends every row).
+ * slot_row: device int32 [B] or NULL: row b reads cache row max(slot_row[b], 0) of caches [rows][H][s_cap][64]; -1 = idle slot.
+ *   Entries outside [-1, rows) are refused (the table is read back and checked before the launch).  Without it rows >= B.
+ * kv_half: caches IEEE half; nt: 1 non-temporal K/V loads, 0 default policy (what wt_decoder_begin picks for small steps);
+ * n_split 1..16; defer_merge (n_split >= 2): the partials stay in `part` [B][H][n_split][68] for the consumer, no ticket, `out` unused.
+ * ln_h / ln_r / ln_t: all NULL (plain query) or all set (folded query).  part / cnt / out as wt_dbg_decode_attention.
+ * Returns -22 without launching on any argument outside these ranges (B > 16, a partial LayerNorm set, a length outside the cache, ...). */
+size_t wt_dbg_decode_attention_state_scratch_bytes(void);
+int wt_dbg_decode_attention_state(const float* q, const void* kcache, const void* vcache, float* part, int* cnt, float* out,
+                                  const int32_t* self_len, int fixed_len, const int32_t* alive, const int32_t* slot_row, int rows,
+                                  const float* ln_h, const float* ln_r, const float* ln_t, int B, int H, int s_cap, int n_split, int kv_half,
+                                  int nt, int defer_merge, void* scratch, void* stream);
+/* wt_dbg_self_attention_then_pair as the step graph runs it (LP_SELF_ATTN with two splits and the merge deferred, then LP_PAIR): the key
+ * count per row from the device state -- self_len a HOST int32 [B] as above -- or one fixed_len > 0 for all rows (exactly one of the two).
+ * half: caches and both weight matrices IEEE half (an fp16 decoder engine), else all float; nt as above (the engine passes one flag to
+ * both launches).  scratch: wt_dbg_self_attention_then_pair_state_scratch_bytes() bytes. */
+size_t wt_dbg_self_attention_then_pair_state_scratch_bytes(void);
+int wt_dbg_self_attention_then_pair_state(const float* q, const void* kcache, const void* vcache, float* part, const void* Wo, const float* bo,
+                                          const float* h, float* h1, const void* Wf, const float* c, float* u, const int32_t* self_len,
+                                          int fixed_len, int B, int H, int s_cap, int half, int nt, void* scratch, void* stream);
 /* a beam decode in flight: the plain logits of the last executed step, device f32 [rows][V] */
 int wt_dbg_beam_logits(wt_engine* dec, float* logits_out, void* stream);
 /* a beam decode in flight: per executed step and row (token, source beam within the utterance, score bits, utterance done), device int32

@@ -35,7 +35,9 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_token_timestamps_scratch_bytes", "wt_dbg_token_timestamp_matrix_kernels", "wt_dbg_token_timestamp_median",
                  "wt_dbg_token_timestamp_dtw", "wt_dbg_token_timestamp_q_hist", "wt_dbg_token_timestamp_matrix", "wt_dbg_cross_k_head",
                  "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes",
-                 "wt_dbg_logprob_select_scratch_bytes", "wt_dbg_logprob_select"]
+                 "wt_dbg_logprob_select_scratch_bytes", "wt_dbg_logprob_select",
+                 "wt_dbg_decode_attention_state_scratch_bytes", "wt_dbg_decode_attention_state",
+                 "wt_dbg_self_attention_then_pair_state_scratch_bytes", "wt_dbg_self_attention_then_pair_state"]
 
 
 class TensorDesc(Structure):
@@ -207,6 +209,12 @@ def load():
     lib.wt_dbg_logprob_select_scratch_bytes.argtypes = [I, I, I]
     lib.wt_dbg_logprob_select_scratch_bytes.restype = c_size_t
     lib.wt_dbg_logprob_select.argtypes = [I, P, P, I, P, P, POINTER(c_int32), P, I, I, I, I, I, I, I, I, POINTER(TimestampParams), I, P, P, P, P, P]
+    lib.wt_dbg_decode_attention_state_scratch_bytes.argtypes = []
+    lib.wt_dbg_decode_attention_state_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_decode_attention_state.argtypes = [P, P, P, P, P, P, POINTER(c_int32), I, P, P, I, P, P, P, I, I, I, I, I, I, I, P, P]
+    lib.wt_dbg_self_attention_then_pair_state_scratch_bytes.argtypes = []
+    lib.wt_dbg_self_attention_then_pair_state_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_self_attention_then_pair_state.argtypes = [P, P, P, P, P, P, P, P, P, P, P, POINTER(c_int32), I, I, I, I, I, I, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

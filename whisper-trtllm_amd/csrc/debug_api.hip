@@ -499,6 +499,85 @@ extern "C" int wt_dbg_skinny_qkv_append(const float* X, const float* ln_w, const
     return rc_of(launch_skinny(k, s));
 }
 
+// ---- decode attention as the step graph launches it: the length per row from a device DecState (fixed_len = 0), the skip-finished-rows
+// and slot_row forms, either load policy ----
+// a host DecState with self_len[b] = self_len[b] (b < B), refusing a length outside the cache
+static bool dbg_self_len_state(DecState& h, const int32_t* self_len, int B, int s_cap) {
+    memset(&h, 0, sizeof h);
+    for (int b = 0; b < MAX_ROWS; ++b) { h.slot_row[b] = -1; h.row_force[b] = -1; }
+    for (int b = 0; b < B; ++b) {
+        if (self_len[b] < 0 || self_len[b] >= s_cap) return false;
+        h.self_len[b] = self_len[b];
+    }
+    return true;
+}
+extern "C" size_t wt_dbg_decode_attention_state_scratch_bytes(void) { return dbg_align(sizeof(DecState)); }
+extern "C" int wt_dbg_decode_attention_state(const float* q, const void* kcache, const void* vcache, float* part, int* cnt, float* out,
+                                             const int32_t* self_len, int fixed_len, const int32_t* alive, const int32_t* slot_row, int rows,
+                                             const float* ln_h, const float* ln_r, const float* ln_t, int B, int H, int s_cap, int n_split,
+                                             int kv_half, int nt, int defer_merge, void* scratch, void* stream) {
+    if (!q || !kcache || !vcache || B < 1 || B > MAX_ROWS || H < 1 || H * 64 > 1024 || s_cap < 1 || n_split < 1 || n_split > 16) return -22;
+    if ((nt != 0 && nt != 1) || (kv_half != 0 && kv_half != 1) || (defer_merge != 0 && defer_merge != 1)) return -22;
+    if ((ln_h || ln_r || ln_t) && !(ln_h && ln_r && ln_t)) return -22;
+    if ((self_len != nullptr) == (fixed_len > 0) || fixed_len < 0 || fixed_len > s_cap) return -22;   // exactly one source of the length
+    if (self_len && !scratch) return -22;
+    if (defer_merge ? (n_split < 2 || !part) : (!out || (n_split > 1 && (!part || !cnt)))) return -22;
+    if (rows < 1 || (!slot_row && rows < B)) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (slot_row) {   // device table: checked on the host before anything is launched
+        int32_t host_rows[MAX_ROWS];
+        if ((rc = rc_of(hipMemcpyAsync(host_rows, slot_row, (size_t)B * 4, hipMemcpyDeviceToHost, s)))) return rc;
+        if ((rc = rc_of(hipStreamSynchronize(s)))) return rc;
+        for (int b = 0; b < B; ++b)
+            if (host_rows[b] < -1 || host_rows[b] >= rows) return -22;
+    }
+    DecAttnParams a;
+    memset(&a, 0, sizeof a);
+    if (self_len) {
+        DecState h;
+        if (!dbg_self_len_state(h, self_len, B, s_cap)) return -22;
+        if ((rc = upload_state(scratch, h, s))) return rc;
+        a.st = (const DecState*)scratch;
+    }
+    a.q = q; a.kcache = (const float*)kcache; a.vcache = (const float*)vcache; a.part = part; a.cnt = cnt; a.out = out; a.B = B; a.H = H;
+    a.s_cap = s_cap; a.n_split = n_split; a.fixed_len = fixed_len; a.nt = nt; a.kv_half = kv_half; a.defer_merge = defer_merge;
+    a.alive = alive; a.slot_row = slot_row; a.ln_h = ln_h; a.ln_r = ln_r; a.ln_t = ln_t;
+    return rc_of(launch_dec_attn(a, s));
+}
+extern "C" size_t wt_dbg_self_attention_then_pair_state_scratch_bytes(void) { return dbg_align(sizeof(DecState)); }
+extern "C" int wt_dbg_self_attention_then_pair_state(const float* q, const void* kcache, const void* vcache, float* part, const void* Wo,
+                                                    const float* bo, const float* h, float* h1, const void* Wf, const float* c, float* u,
+                                                    const int32_t* self_len, int fixed_len, int B, int H, int s_cap, int half, int nt,
+                                                    void* scratch, void* stream) {
+    if (!q || !kcache || !vcache || !part || !Wo || !bo || !h || !h1 || !Wf || !c || !u) return -22;
+    if (B < 1 || B > MAX_ROWS || H < 1 || H * 64 > 1024 || s_cap < 1 || (nt != 0 && nt != 1) || (half != 0 && half != 1)) return -22;
+    if ((self_len != nullptr) == (fixed_len > 0) || fixed_len < 0 || fixed_len > s_cap || (self_len && !scratch)) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    const int d = H * 64;
+    DecAttnParams a;
+    memset(&a, 0, sizeof a);
+    if (self_len) {
+        DecState hs;
+        if (!dbg_self_len_state(hs, self_len, B, s_cap)) return -22;
+        const int rc = upload_state(scratch, hs, s);
+        if (rc) return rc;
+        a.st = (const DecState*)scratch;
+    }
+    a.q = q; a.kcache = (const float*)kcache; a.vcache = (const float*)vcache; a.part = part; a.B = B; a.H = H; a.s_cap = s_cap; a.n_split = 2;
+    a.fixed_len = fixed_len; a.nt = nt; a.kv_half = half; a.defer_merge = 1;
+    int rc = rc_of(launch_dec_attn(a, s));
+    if (rc) return rc;
+    SkinnyParams k, k2;
+    memset(&k, 0, sizeof k);
+    memset(&k2, 0, sizeof k2);
+    k.parts = part; k.parts_nsplit = 2; k.parts_H = H; k.W = (const float*)Wo; k.bias = bo; k.resid = h; k.Y = h1; k.B = B; k.N = d; k.K = d;
+    k.q_scale = 1.f; k.w_nt = nt; k.w_half = half; k.st = a.st;
+    k2.parts = part; k2.parts_nsplit = 2; k2.parts_H = H; k2.X2 = h; k2.x_direct = 1; k2.W = (const float*)Wf; k2.bias = c; k2.Y = u; k2.B = B;
+    k2.N = d; k2.K = 2 * d; k2.q_scale = 1.f; k2.w_nt = nt; k2.w_half = half; k2.st = a.st;
+    return rc_of(launch_skinny_pair(k, k2, s));
+}
+
 static void dbg_state_to_dev(const int32_t* w, DecState& h) {
     memset(&h, 0, sizeof h);
     h.done = w[0]; h.n_unfinished = w[1]; h.step = w[2]; h.seq = w[3];
