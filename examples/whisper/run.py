@@ -63,6 +63,13 @@ def parse_arguments():
                         "log-probability with --return_token_timestamps; needs a batch plan, no beams")
     parser.add_argument("--no_speech_token_id", type=int, default=None, help="the <|nospeech|> (<|nocaptions|>) id whose first-step probability "
                         "--return_logprobs reports as no_speech_prob")
+    parser.add_argument("--temperature", type=float, default=0.0, help="fast path: sample every token from softmax(scores / T) on the device "
+                        "instead of the argmax (utterance i draws with seed --seed + i); implies --return_logprobs; needs a batch plan, no beams")
+    parser.add_argument("--seed", type=int, default=0, help="base seed of --temperature / --temperature_fallback")
+    parser.add_argument("--temperature_fallback", action="store_true", help="fast path: openai-whisper's quality loop -- decode greedily, "
+                        "then decode the utterances whose transcript is repetitive (compression ratio > 2.4) or unlikely (avg_logprob < -1) "
+                        "again at temperature 0.2, 0.4 .. 1.0 (not those whose no_speech_prob > 0.6, with --no_speech_token_id); implies "
+                        "--return_logprobs; prints the temperature used per utterance")
     parser.add_argument("--length_penalty", type=float, default=1.0)
     parser.add_argument("--early_stopping", action="store_true")
     args = parser.parse_args()
@@ -74,6 +81,12 @@ def parse_arguments():
     if args.return_token_timestamps and (args.batching == "continuous" or args.num_beams > 1 or args.session):
         parser.error("--return_token_timestamps needs the fast path with a batch plan (--batching sorted | dataset) and no beams: the "
                      "continuous mode keeps no query history, beam search no beam_indices, the Session path no cross attentions")
+    if args.temperature_fallback and (args.temperature > 0 or args.return_token_timestamps):
+        parser.error("--temperature_fallback takes no --temperature (it walks 0, 0.2 .. 1.0) and no --return_token_timestamps")
+    if not (args.temperature >= 0 and args.temperature < float("inf")):
+        parser.error("--temperature must be a finite number >= 0")
+    if args.temperature > 0 or args.temperature_fallback:
+        args.return_logprobs = True
     if args.return_logprobs and (args.batching == "continuous" or args.num_beams > 1 or args.session):
         parser.error("--return_logprobs needs the fast path with a batch plan (--batching sorted | dataset) and no beams")
     if args.no_speech_token_id is not None and not args.return_logprobs:
@@ -222,13 +235,22 @@ if __name__ == "__main__":
                 if args.return_logprobs:
                     lp = {"return_logprobs": True, "no_speech_token_id": args.no_speech_token_id}
                     kw = [dict(k, **lp) for k in (kw or [{}] * len(groups))]
+                if args.temperature > 0:             # utterance i draws with seed + i, whichever batch it lands in
+                    kw = [dict(k, temperature=args.temperature, seeds=[args.seed + i for i in g]) for k, g in zip(kw, groups)]
+                if args.temperature_fallback:
+                    kw = [{"return_timestamps": args.return_timestamps, "no_speech_token_id": args.no_speech_token_id,
+                           "temperature_fallback": {"seeds": [args.seed + i for i in g]}} for g in groups]
                 if args.num_beams > 1:
                     kw = [{"num_beams": args.num_beams, "length_penalty": args.length_penalty, "early_stopping": args.early_stopping}] * len(groups)
                 for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):
+                    used = [args.temperature] * len(g)
+                    if args.temperature_fallback:        # (ids, DecodeScores, temperature used per row)
+                        used = ids[2].cpu().tolist()
+                        ids = ids[:2]
                     if args.return_logprobs:             # (ids, [seconds per token,] DecodeScores) of the batch
                         sc = ids[-1]
                         nsp = sc.no_speech_prob.cpu().tolist() if sc.no_speech_prob is not None else [None] * len(g)
-                        score_rows += list(zip(g, zip(sc.token_logprobs.cpu().tolist(), sc.avg_logprob.cpu().tolist(), nsp)))
+                        score_rows += list(zip(g, zip(sc.token_logprobs.cpu().tolist(), sc.avg_logprob.cpu().tolist(), nsp, used)))
                         ids = ids[:-1] if args.return_token_timestamps else ids[0]
                     if args.return_token_timestamps:     # (ids, seconds per token) of the batch
                         indexed += list(zip(g, zip(ids[0].cpu().tolist(), ids[1].cpu().tolist())))
@@ -295,11 +317,13 @@ if __name__ == "__main__":
     if rank == 0 and scores is not None:             # confidence per utterance (openai-whisper's segment fields)
         tok = tensorrt_llm.text.WhisperTokenDecoder.from_dir(args.whisper) if os.path.isdir(args.whisper) else None
         eos, pad = config["eos_token_id"], config["pad_token_id"]
-        for i, (ids, (_lps, avg, nsp)) in enumerate(zip(results["fast"][1], scores)):
+        sampled = args.temperature > 0 or args.temperature_fallback
+        for i, (ids, (_lps, avg, nsp, used)) in enumerate(zip(results["fast"][1], scores)):
             # without a tokenizer the ratio is taken over the ids written out: repetition still shows
             text = tok.decode(ids, skip_special_tokens=True) if tok else " ".join(str(t) for t in trim_after_eos(ids, eos, pad))
             ratio = tensorrt_llm.text.compression_ratio(text) if text else 0.0
-            print(f"utterance {i}: avg_logprob {avg:.6f}  no_speech_prob {'n/a' if nsp is None else format(nsp, '.6f')}  compression_ratio {ratio:.3f}")
+            print(f"utterance {i}: avg_logprob {avg:.6f}  no_speech_prob {'n/a' if nsp is None else format(nsp, '.6f')}  compression_ratio {ratio:.3f}"
+                  + (f"  temperature {used:.1f}" if sampled else ""))
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -261,6 +261,36 @@ typedef struct {
 int wt_decoder_set_logprobs(wt_engine* dec, const wt_logprob_params* p);
 int wt_decoder_read_logprobs(wt_engine* dec, float* token_logprobs, int ld, float* sum_logprob, float* no_speech_prob, void* stream);
 
+/* (9f) temperature sampling for the batch decode (wt_decoder_begin / _steps / _run / _greedy), on the device, where the argmax lives: the
+ * logits still never reach memory.  A draw from softmax(s / T) is argmax_v (s[v] / T + g[v]) with independent standard Gumbel noise g
+ * (the Gumbel-max identity), so the vocabulary projection's argmax epilogue, the select kernels and the finish kernel keep their
+ * structure and compare a key instead of a score.  With s = the step's scores after every processor it applies (Suppress ->
+ * SuppressAtBegin -> Force -> the timestamp rules), the row b that writes sequence position t (its current length, prompt included) takes
+ *   x   = Philox4x32-10(counter = (v >> 2, t, 0, 0), key = (seed[b] & 0xffffffff, seed[b] >> 32))[v & 3]
+ *   u   = ((x >> 9) + 0.5) * 2^-23            (exact in fp32, strictly inside (0, 1))
+ *   key = s[v] / T + (-logf(-logf(u)))        (fp32; s / T is transformers' TemperatureLogitsWarper)
+ * and the token is the NaN-aware argmax of key, the lowest id among equals.  -inf stays -inf, a NaN score ranks first as it does in the
+ * greedy decode, a forced position yields the forced token.  The generator is counter-based: a draw depends on (seed, position, id)
+ * alone -- not on the batch slot, the batch size, the fused or non-fused path or the order of anything -- and is bitwise repeatable.  In
+ * timestamp mode (9b) the rules use the unperturbed scores (the timestamps' log-sum-exp against the best text score, the forced <|0.00|>)
+ * and the token is the best key among the ids the rules leave.
+ * A sampled decode runs with the log-probability mode (9e) on, whether or not wt_decoder_set_logprobs asked for it, and its entries are
+ * those of the UNTEMPERED scores: token_logprob = s[tok] - logsumexp(s), openai-whisper's definition (GreedyDecoder.update takes
+ * log_softmax(logits) and samples from logits / temperature).
+ * seeds: n_seeds 64-bit row seeds (host pointer, copied by the call), or NULL: row b uses seed + b.
+ * The setting applies from the next wt_decoder_begin on this handle; p == NULL or temperature <= 0 turns it off, and the engine then
+ * enqueues exactly what it did before.  WT_E_INVALID for a temperature that is not finite; wt_decoder_begin returns WT_E_INVALID when the
+ * seed list is shorter than its batch, refuses (WT_E_UNSUPPORTED) sampling together with beam search, and wt_decoder_stream_begin refuses
+ * it.  It combines with the timestamp mode (9b), token-level timestamps (9d), the log-probability mode (9e), logits_trace and
+ * force_eos_step(s).  One temperature per call; no top-k / top-p warpers, no best_of. */
+typedef struct {
+    float temperature;            /* <= 0: sampling off (greedy) */
+    const uint64_t* seeds;        /* host pointer [batch of the next begin], copied by the call; NULL: seed + row */
+    int32_t n_seeds;
+    uint64_t seed;
+} wt_sampling_params;
+int wt_decoder_set_sampling(wt_engine* dec, const wt_sampling_params* p);
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

@@ -226,6 +226,18 @@ int wt_dbg_logprob_select(int form, const float* X, const float* W, int K, const
                           int32_t* ids, int B, int V, int max_length, int cur_len, int step, int begin_index, int eos, int force_eos_step,
                           const wt_timestamp_params* t, int no_speech_token_id, float* logprob_out, float* sum_out, float* no_speech_out,
                           void* scratch, void* stream);
+/* The same tail in its temperature-sampling form (wt_decoder_set_sampling): the arguments of wt_dbg_logprob_select plus the temperature
+ * (> 0) and `seeds`, a HOST array of B 64-bit row seeds.  form 0: the vocabulary GEMV's sampling epilogue over X, W, then
+ * greedy_finish_kernel<false, true, true>; form 1: sample_select_kernel over `logits`, in the partition of form 0's GEMV for this K (so K is needed here too), or, with `t` given, the timestamp mode's
+ * ts_select_kernel<true, true> + greedy_finish_kernel<true, true, true>.  Position cur_len of `ids` receives the drawn token, logprob_out
+ * its log-probability under the UNTEMPERED scores, key_out f32 [B] (device) the key it won with (in timestamp mode: the best key among
+ * the ids the rules leave, also at the forced <|0.00|>).  scratch: wt_dbg_sample_select_scratch_bytes(B, V, max_length) bytes.
+ * Synchronises `stream`. */
+size_t wt_dbg_sample_select_scratch_bytes(int B, int V, int max_length);
+int wt_dbg_sample_select(int form, const float* X, const float* W, int K, const float* logits, const unsigned char* mask, const int32_t* forced,
+                         int32_t* ids, int B, int V, int max_length, int cur_len, int step, int begin_index, int eos, int force_eos_step,
+                         const wt_timestamp_params* t, int no_speech_token_id, float temperature, const uint64_t* seeds, float* logprob_out,
+                         float* sum_out, float* no_speech_out, float* key_out, void* scratch, void* stream);
 /* step 0's input: x[b] = tok_emb[ids[b][cur_len[b] - 1]] + pos_emb[pos[b]]; ids [B][ids_ld], cur_len, pos: HOST arrays; tok_emb [V][d] float
  * or half (emb_half), pos_emb [pos_rows][d].  scratch: wt_dbg_dec_embed_scratch_bytes(B, ids_ld) bytes. */
 size_t wt_dbg_dec_embed_scratch_bytes(int B, int ids_ld);

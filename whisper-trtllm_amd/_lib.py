@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "lib", "libwhisper_trtllm_amd.so")
@@ -18,7 +18,7 @@ EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
     "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores",
-    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_set_sampling", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
     "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_last_error", "wt_abi_version",
 ]
@@ -36,6 +36,7 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_token_timestamp_dtw", "wt_dbg_token_timestamp_q_hist", "wt_dbg_token_timestamp_matrix", "wt_dbg_cross_k_head",
                  "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes",
                  "wt_dbg_logprob_select_scratch_bytes", "wt_dbg_logprob_select",
+                 "wt_dbg_sample_select_scratch_bytes", "wt_dbg_sample_select",
                  "wt_dbg_decode_attention_state_scratch_bytes", "wt_dbg_decode_attention_state",
                  "wt_dbg_self_attention_then_pair_state_scratch_bytes", "wt_dbg_self_attention_then_pair_state"]
 
@@ -76,6 +77,10 @@ class TokenTimestampParams(Structure):
 
 class LogprobParams(Structure):
     _fields_ = [("enabled", c_int32), ("no_speech_token_id", c_int32)]
+
+
+class SamplingParams(Structure):
+    _fields_ = [("temperature", c_float), ("seeds", POINTER(c_uint64)), ("n_seeds", c_int32), ("seed", c_uint64)]
 
 
 class KernelTimer(Structure):
@@ -130,6 +135,7 @@ def load():
     lib.wt_decoder_read_token_timestamps.argtypes = [c_void_p, c_void_p, c_int, c_void_p]
     lib.wt_decoder_set_logprobs.argtypes = [c_void_p, POINTER(LogprobParams)]
     lib.wt_decoder_read_logprobs.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    lib.wt_decoder_set_sampling.argtypes = [c_void_p, POINTER(SamplingParams)]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -209,6 +215,10 @@ def load():
     lib.wt_dbg_logprob_select_scratch_bytes.argtypes = [I, I, I]
     lib.wt_dbg_logprob_select_scratch_bytes.restype = c_size_t
     lib.wt_dbg_logprob_select.argtypes = [I, P, P, I, P, P, POINTER(c_int32), P, I, I, I, I, I, I, I, I, POINTER(TimestampParams), I, P, P, P, P, P]
+    lib.wt_dbg_sample_select_scratch_bytes.argtypes = [I, I, I]
+    lib.wt_dbg_sample_select_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_sample_select.argtypes = [I, P, P, I, P, P, POINTER(c_int32), P, I, I, I, I, I, I, I, I, POINTER(TimestampParams), I, F,
+                                         POINTER(c_uint64), P, P, P, P, P, P]
     lib.wt_dbg_decode_attention_state_scratch_bytes.argtypes = []
     lib.wt_dbg_decode_attention_state_scratch_bytes.restype = c_size_t
     lib.wt_dbg_decode_attention_state.argtypes = [P, P, P, P, P, P, POINTER(c_int32), I, P, P, I, P, P, P, I, I, I, I, I, I, I, P, P]

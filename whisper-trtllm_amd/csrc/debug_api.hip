@@ -708,6 +708,81 @@ extern "C" int wt_dbg_logprob_select(int form, const float* X, const float* W, i
     return rc_of(hipStreamSynchronize(s));
 }
 
+// ---- temperature sampling: the same launches in their sampling form (form 0: the vocabulary GEMV's epilogue from X, W; form 1: the select
+// kernel from logits, the timestamp-mode pair when `t` is given), then the finish kernel ----
+struct SmScratch { size_t seeds, sc, ts, key, total; };
+static SmScratch sm_scratch_layout(int B, int V, int max_length) {
+    SmScratch l;
+    size_t off = lp_scratch_layout(B, V, max_length).total;
+    auto take = [&](size_t bytes) { const size_t o = off; off = dbg_align(off + bytes); return o; };
+    const size_t parts = (size_t)(V / 2 + SELECT_CHUNKS + 1);
+    l.seeds = take((size_t)B * 8); l.sc = take((size_t)B * parts * 4); l.ts = take((size_t)B * SELECT_CHUNKS * sizeof(float4)); l.key = take((size_t)B * 4);
+    l.total = off;
+    return l;
+}
+extern "C" size_t wt_dbg_sample_select_scratch_bytes(int B, int V, int max_length) {
+    if (B < 1 || B > MAX_ROWS || V < 1 || max_length < 2) return 0;
+    return sm_scratch_layout(B, V, max_length).total;
+}
+extern "C" int wt_dbg_sample_select(int form, const float* X, const float* W, int K, const float* logits, const unsigned char* mask,
+                                    const int32_t* forced, int32_t* ids, int B, int V, int max_length, int cur_len, int step, int begin_index,
+                                    int eos, int force_eos_step, const wt_timestamp_params* t, int no_speech_token_id, float temperature,
+                                    const uint64_t* seeds, float* logprob_out, float* sum_out, float* no_speech_out, float* key_out,
+                                    void* scratch, void* stream) {
+    if (form < 0 || form > 1 || !mask || !forced || !ids || !logprob_out || !sum_out || !key_out || !seeds || !scratch) return -22;
+    if (!(temperature > 0.f) || !(temperature <= 3.4028235e38f)) return -22;
+    if (B < 1 || B > MAX_ROWS || V < 1 || max_length < 2 || cur_len < 1 || cur_len >= max_length || step < 0) return -22;
+    if (eos < 0 || eos >= V || no_speech_token_id >= V || (no_speech_token_id >= 0 && !no_speech_out)) return -22;
+    if (form == 0 ? (!X || !W || t) : !logits) return -22;
+    if (!t && (K < 8 || K > 1024 || (K & 7))) return -22;   // form 1 walks the logits in the partition of form 0's GEMV for this K
+    for (int i = 0; i < max_length; ++i)
+        if (forced[i] >= V) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    const LpScratch l = lp_scratch_layout(B, V, max_length);
+    const SmScratch m = sm_scratch_layout(B, V, max_length);
+    char* base = (char*)scratch;
+    DecState h;
+    memset(&h, 0, sizeof h);
+    h.step = step;
+    for (int b = 0; b < MAX_ROWS; ++b) {
+        h.cur_len[b] = cur_len; h.pos[b] = cur_len - 1; h.self_len[b] = cur_len - 1; h.slot_row[b] = -1; h.row_force[b] = -1;
+    }
+    int unf[MAX_ROWS];
+    for (int b = 0; b < MAX_ROWS; ++b) unf[b] = 1;
+    int rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.forced, forced, (size_t)max_length * 4, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + l.unf, unf, (size_t)B * 4, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(base + m.seeds, seeds, (size_t)B * 8, hipMemcpyHostToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemsetAsync(base + l.tok, 0, (size_t)B * max_length * 4, s)))) return rc;
+    if ((rc = rc_of(hipMemsetAsync(base + l.side, 0, (size_t)B * 2 * 4, s)))) return rc;
+    if ((rc = rc_of(hipMemsetAsync(sum_out, 0, (size_t)B * 4, s)))) return rc;
+    if ((rc = upload_state(base + l.st, h, s))) return rc;
+    SelectParams p;
+    greedy_select_params(p, form == 0 ? (const float*)(base + l.lg) : logits, mask, (const int*)(base + l.forced), ids, (int*)(base + l.unf),
+                         (DecState*)(base + l.st), nullptr, (float*)(base + l.pv), (int*)(base + l.pi), nullptr, nullptr, nullptr, 0, 0, B, V,
+                         max_length, begin_index, eos, eos, force_eos_step, nullptr, nullptr, 0);
+    p.lp_on = 1; p.lp_ns = no_speech_token_id; p.lp_part = (float4*)(base + l.lpp); p.lp_side = (float*)(base + l.side);
+    p.lp_tok = (float*)(base + l.tok); p.lp_sum = sum_out; p.lp_nsp = no_speech_out;
+    p.samp_on = 1; p.samp_temp = temperature; p.samp_seeds = (const unsigned long long*)(base + m.seeds); p.samp_sc = (float*)(base + m.sc);
+    p.samp_ts = (float4*)(base + m.ts); p.samp_key = (float*)(base + m.key);
+    p.samp_K = K; p.samp_parts_cap = V / 2 + SELECT_CHUNKS + 1;
+    if (t) {
+        p.ts_on = 1; p.no_ts = t->no_timestamps_token_id; p.tb = t->timestamp_begin; p.ts_begin_index = t->begin_index;
+        p.max_init = t->max_initial_timestamp_index; p.ts_part = (TsPart*)(base + l.tsp);
+    }
+    if (form == 0) {
+        SkinnyParams k = dbg_vocab_params(X, nullptr, nullptr, W, nullptr, nullptr, (const DecState*)(base + l.st), B, V, K, 0, 0, 0);
+        const int grid = vocab_skinny_fuse_argmax(k, p);
+        if (grid < 1 || grid > V / 2 + SELECT_CHUNKS + 1) return -22;
+        if ((rc = rc_of(launch_skinny(k, s)))) return rc;
+        greedy_select_fused(p, grid);
+    }
+    if ((rc = rc_of(launch_greedy_select(p, s)))) return rc;
+    if ((rc = rc_of(hipMemcpy2DAsync(logprob_out, 4, p.lp_tok + cur_len, (size_t)max_length * 4, 4, B, hipMemcpyDeviceToDevice, s)))) return rc;
+    if ((rc = rc_of(hipMemcpyAsync(key_out, base + m.key, (size_t)B * 4, hipMemcpyDeviceToDevice, s)))) return rc;
+    return rc_of(hipStreamSynchronize(s));
+}
+
 extern "C" size_t wt_dbg_dec_embed_scratch_bytes(int B, int ids_ld) {
     return B < 1 || ids_ld < 1 ? 0 : dbg_align(sizeof(DecState)) + dbg_align((size_t)B * ids_ld * 4);
 }

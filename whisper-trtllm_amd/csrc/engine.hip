@@ -5,6 +5,7 @@
 #include "../../include/whisper_trtllm_amd.h"
 #include "wt_common.h"
 
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -151,6 +152,16 @@ struct wt_engine {
     wt_logprob_params lp_req = {0, -1}, lp_cur = {0, -1};
     float4* lp_part = nullptr;    // [dec_cap][SEL_PARTS_CAP]
     float *lp_side = nullptr, *lp_tok = nullptr, *lp_sum = nullptr, *lp_nsp = nullptr;   // [dec_cap][2], [dec_cap][cap_len], [dec_cap], [dec_cap]
+    // temperature sampling: the setting wt_decoder_set_sampling asked for (applied by the next wt_decoder_begin) and the temperature of the
+    // decode in flight (0: greedy; the step graph carries it).  The sampling kernels are forms of the log-probability mode's, so a sampled
+    // decode runs with that mode on.
+    float samp_req_temp = 0.f, samp_cur_temp = 0.f;
+    unsigned long long samp_req_seed = 0;
+    std::vector<unsigned long long> samp_req_seeds;   // empty: seed + row
+    bool samp_req_list = false;
+    unsigned long long* samp_seeds = nullptr;   // [dec_cap]
+    float* samp_sc = nullptr;                   // [dec_cap][SEL_PARTS_CAP]
+    float4* samp_ts = nullptr;                  // [dec_cap][SELECT_CHUNKS]
     // beam search: the setting wt_decoder_set_beam_search asked for (applied by the next wt_decoder_begin) and that of the decode in
     // flight (num_beams <= 1: off).  In a beam decode B = beam_U * num_beams rows.
     wt_beam_params beam_req = {1, 1.f, 0}, beam_cur = {1, 1.f, 0};
@@ -694,6 +705,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     const size_t o_tsp = take((size_t)B * SELECT_CHUNKS * sizeof(TsPart));
     const size_t o_lpp = take((size_t)B * SEL_PARTS_CAP * sizeof(float4)), o_lps = take((size_t)B * 2 * 4), o_lpt = take((size_t)B * cap_len * 4);
     const size_t o_lpsum = take((size_t)B * 4), o_lpn = take((size_t)B * 4);
+    const size_t o_sseed = take((size_t)B * 8), o_ssc = take((size_t)B * SEL_PARTS_CAP * 4), o_sts = take((size_t)B * SELECT_CHUNKS * sizeof(float4));
     // beam search state (BeamParams): sized for MAX_ROWS rows whatever B, it is small
     const size_t o_bpart = take((size_t)MAX_ROWS * SELECT_CHUNKS * sizeof(BeamPart)), o_bsc = take(MAX_ROWS * 4), o_bids2 = take((size_t)MAX_ROWS * cap_len * 4);
     const size_t o_banc = take((size_t)2 * MAX_ROWS * cap_len * 4), o_burow = take(MAX_ROWS * 4), o_bhn = take(MAX_ROWS * 4), o_bhd = take(MAX_ROWS * 4);
@@ -707,6 +719,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     e->logits = (float*)(b + o_lg); e->st = (DecState*)(b + o_st); e->ids = (int*)(b + o_ids); e->unfinished = (int*)(b + o_unf);
     e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows); e->ts_part = (TsPart*)(b + o_tsp);
     e->lp_part = (float4*)(b + o_lpp); e->lp_side = (float*)(b + o_lps); e->lp_tok = (float*)(b + o_lpt); e->lp_sum = (float*)(b + o_lpsum); e->lp_nsp = (float*)(b + o_lpn);
+    e->samp_seeds = (unsigned long long*)(b + o_sseed); e->samp_sc = (float*)(b + o_ssc); e->samp_ts = (float4*)(b + o_sts);
     {
         BeamParams& bp = e->beam_dev;
         memset(&bp, 0, sizeof bp);
@@ -1149,6 +1162,24 @@ extern "C" int wt_decoder_set_logprobs(wt_engine* e, const wt_logprob_params* p)
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_sampling(wt_engine* e, const wt_sampling_params* p) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_sampling: not a decoder engine");
+    if (p && !(fabsf(p->temperature) <= 3.4028235e38f)) return fail(WT_E_INVALID, "wt_decoder_set_sampling: temperature is not finite");
+    if (!p || !(p->temperature > 0.f)) {
+        e->samp_req_temp = 0.f;
+        e->samp_req_list = false;
+        e->samp_req_seeds.clear();
+        return WT_OK;
+    }
+    if (p->seeds && p->n_seeds < 1) return fail(WT_E_INVALID, "wt_decoder_set_sampling: a seed list of %d entries", p->n_seeds);
+    e->samp_req_temp = p->temperature;
+    e->samp_req_seed = p->seed;
+    e->samp_req_list = p->seeds != nullptr;
+    e->samp_req_seeds.clear();
+    if (p->seeds) e->samp_req_seeds.assign(p->seeds, p->seeds + p->n_seeds);
+    return WT_OK;
+}
+
 // the log-probability setting of the decode that is starting (a changed one re-captures the step graphs)
 static void lp_apply(wt_engine* e, const wt_logprob_params lp) {
     if (memcmp(&e->lp_cur, &lp, sizeof lp) != 0) e->graph_valid = false;
@@ -1171,16 +1202,35 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
             return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: logits_trace / force_eos_step(s) are not available with beam search");
         if (e->lp_req.enabled)
             return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token log-probabilities cannot be combined (wt_decoder_read_beam_scores is the beams' score)");
+        if (e->samp_req_temp > 0.f)
+            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and temperature sampling cannot be combined");
         if (U * nb > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", U, nb, MAX_ROWS);
         B = U * nb;
     }
+    const float samp_temp = e->samp_req_temp;
+    if (samp_temp > 0.f && e->samp_req_list && (int)e->samp_req_seeds.size() < B)
+        return fail(WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_sampling gave %d seeds for a batch of %d", (int)e->samp_req_seeds.size(), B);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
     int rc = decode_setup(e, B, p, 0, false, s, "wt_decoder_begin", nb > 1 ? beam : wt_beam_params{1, 1.f, 0});
     if (rc) return rc;
     e->beam_U = U;
-    lp_apply(e, e->lp_req);
+    {   // temperature sampling runs the log-probability mode's kernels in their sampling form
+        wt_logprob_params lp = e->lp_req;
+        if (samp_temp > 0.f) lp.enabled = 1;
+        lp_apply(e, lp);
+        if (samp_temp != e->samp_cur_temp) e->graph_valid = false;   // the step graph carries the temperature
+        e->samp_cur_temp = samp_temp;
+        if (samp_temp > 0.f) {
+            std::vector<unsigned long long>& h = e->samp_req_seeds;   // (kept alive by the handle: the copy below may read it later)
+            if (!e->samp_req_list) {
+                h.resize(B);
+                for (int b = 0; b < B; ++b) h[b] = e->samp_req_seed + (unsigned long long)b;
+            }
+            HIPCHK(hipMemcpyAsync(e->samp_seeds, h.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
+        }
+    }
     if (e->lp_cur.enabled) {   // position 0, the positions behind an EOS and the sums start at zero
         HIPCHK(hipMemsetAsync(e->lp_tok, 0, (size_t)B * p->max_length * 4, s));
         HIPCHK(hipMemsetAsync(e->lp_sum, 0, (size_t)B * 4, s));
@@ -1220,6 +1270,10 @@ static void fill_select_params(wt_engine* e, SelectParams& sp) {
     if (e->lp_cur.enabled && !e->stream_mode) {
         sp.lp_on = 1; sp.lp_ns = e->lp_cur.no_speech_token_id; sp.lp_part = e->lp_part; sp.lp_side = e->lp_side; sp.lp_tok = e->lp_tok;
         sp.lp_sum = e->lp_sum; sp.lp_nsp = e->lp_nsp;
+        if (e->samp_cur_temp > 0.f) {
+            sp.samp_on = 1; sp.samp_temp = e->samp_cur_temp; sp.samp_seeds = e->samp_seeds; sp.samp_sc = e->samp_sc; sp.samp_ts = e->samp_ts;
+            sp.samp_K = e->d; sp.samp_parts_cap = SEL_PARTS_CAP;
+        }
     }
     if (e->stream_mode) {
         sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1; sp.force_eos_rows = nullptr; sp.trace = nullptr;
@@ -1324,6 +1378,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     if (e->beam_req.num_beams > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: beam search is a batch-decode feature (wt_decoder_begin)");
     if (e->tt_req.n_sel > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token-level timestamps are a batch-decode feature (wt_decoder_begin)");
     if (e->lp_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token log-probabilities are a batch-decode feature (wt_decoder_begin)");
+    if (e->samp_req_temp > 0.f) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: temperature sampling is a batch-decode feature (wt_decoder_begin)");
     if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);
@@ -1332,6 +1387,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     int rc = decode_setup(e, slots, p, pool_rows, true, s, "wt_decoder_stream_begin");
     if (rc) return rc;
     lp_apply(e, wt_logprob_params{0, -1});
+    if (e->samp_cur_temp != 0.f) { e->samp_cur_temp = 0.f; e->graph_valid = false; }
     if (pool_rows > e->h_pool_cap || e->dec_maxlen_cap > e->h_ml_cap) {   // pinned report area: ids and final lengths per pool row
         HIPCHK(hipStreamSynchronize(s));   // no step of an earlier stream may still write the old area
         const int rows = pool_rows > e->h_pool_cap ? pool_rows : e->h_pool_cap;

@@ -86,7 +86,10 @@ hipError_t launch_dec_embed(const int* ids, int ids_ld, const float* tok_emb, co
 // LP (log-probability mode, ARGMAX only; wt_decoder_set_logprobs): 1 = every output lane also keeps the online log-sum-exp pair of its masked
 // scores, 2 = and a second pair over the raw logits (no_speech_prob); merged per workgroup through the LDS stage of the candidates, in a
 // fixed order, and written beside am_val / am_idx with one vector store.  A compile-time form: the LP = 0 instantiations are untouched.
-template <int NB, int V, int NW, bool W_NT, bool HALF = false, bool ARGMAX = false, bool WH = false, bool GELU_IN = false, int LP = 0>
+// SAMP (temperature sampling, with LP != 0; wt_decoder_set_sampling): the running argmax compares the Gumbel-max key s / T + g (sample_key)
+// instead of the score s and keeps the winner's s beside it; both go through the candidates' LDS stage.  The pairs are those of s, unchanged.
+template <int NB, int V, int NW, bool W_NT, bool HALF = false, bool ARGMAX = false, bool WH = false, bool GELU_IN = false, int LP = 0,
+          bool SAMP = false>
 __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsplit, const int KS, const int rows_per_group,
                                             const int block) {
     extern __shared__ __attribute__((aligned(16))) float sk_smem[];
@@ -180,6 +183,8 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
     if (staged) {
         // every wave of the block needs (a slice of) the same NB whole rows: stage them once per block through LDS.
         // Wave w loads (and LayerNorm-s) rows w and w + NW; after the barrier each wave pulls its slice of all rows.
+        // (SJ rows per wave: two, or NB / NW where a block has fewer than NB / 2 waves -- the four-wave 16-row sampling form)
+        constexpr int SJ = NB > 2 * NW ? NB / NW : 2;
         bool kfull[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) kfull[v] = (4 * lane + 256 * v) < Ks;
@@ -195,10 +200,10 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
                 be[v] = *reinterpret_cast<const float4*>(p.ln_b + fcol[v]);
             }
         }
-        float4 xv[2][4];
+        float4 xv[SJ][4];
         if (p.parts == nullptr) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            for (int j = 0; j < SJ; ++j) {
                 const int b = min(wave + NW * j, p.B - 1);
 #pragma unroll
                 for (int v = 0; v < 4; ++v) xv[j][v] = *reinterpret_cast<const float4*>(p.X + (size_t)b * Ks + fcol[v]);
@@ -209,10 +214,10 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
             // the activation row is the merge of the attention kernel's split partials (deferred from its tail: no ticket, no
             // write-through stores there).  Same operations in the same order as dec_attn_kernel's own merge -> same bits.
             // exactly two splits (launch_skinny checks): both partials of all 8 chunks are requested before the first use
-            float4 o0[2][4], o1[2][4];
-            float m0[2][4], m1[2][4], l0[2][4], l1[2][4];
+            float4 o0[SJ][4], o1[SJ][4];
+            float m0[SJ][4], m1[SJ][4], l0[SJ][4], l1[SJ][4];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) {
+            for (int j = 0; j < SJ; ++j) {
                 const int b = min(wave + NW * j, p.B - 1);
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
@@ -226,7 +231,7 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
             if (row_begin < row_end) wload(0, row_begin);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+            for (int j = 0; j < SJ; ++j)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const float Mg = fmaxf(fmaxf(-INFINITY, m0[j][v]), m1[j][v]);
@@ -244,12 +249,12 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
                 if (!kfull[v]) g[v] = be[v] = make_float4(0.f, 0.f, 0.f, 0.f);  // gamma = beta = 0 outside the row: padding lanes stay 0
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < SJ; ++j)
 #pragma unroll
             for (int v = 0; v < 4; ++v)
                 if (!kfull[v] || wave + NW * j >= p.B) xv[j][v] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < SJ; ++j) {
             const int b = wave + NW * j;
             if (b >= NB) break;
             if (p.xmode == XMODE_LAYERNORM) {
@@ -350,6 +355,14 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
     float* am_tr = nullptr;
     float lp_m = -INFINITY, lp_s = 0.f, lp_rm = -INFINITY, lp_rs = 0.f;   // LP: (max, sum of exp) of the masked / of the raw scores
     static_assert(LP == 0 || ARGMAX, "the log-sum-exp pairs belong to the ARGMAX epilogue");
+    static_assert(!SAMP || LP != 0, "sampling runs with the log-sum-exp pairs on");
+    float am_sc = -INFINITY;                 // SAMP: score of the running winner (am_best is its key)
+    unsigned long long sm_seed = 0;
+    int sm_t = 0;
+    if constexpr (SAMP) {
+        sm_seed = p.am_seeds[min(my_b, p.B - 1)];
+        sm_t = p.st->cur_len[min(my_b, p.B - 1)];
+    }
     if constexpr (ARGMAX) {
         am_mk[0] = p.am_mask[min(row_begin + my_r, p.N - 1)];
         am_at_begin = p.st->cur_len[min(my_b, p.B - 1)] == p.am_begin_index;
@@ -433,7 +446,17 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
                     lse_add(lp_m, lp_s, v);
                     if (n == p.am_eos) p.am_side[2 * my_b] = v;
                 }
-                if (argmax_better(v, n, am_best, am_bidx)) {
+                if constexpr (SAMP) {
+                    unsigned dr[4];
+                    sample_draws(sm_seed, sm_t, n >> 2, dr);
+                    const int q = n & 3;
+                    const float key = sample_key(v, p.am_temp, q == 0 ? dr[0] : q == 1 ? dr[1] : q == 2 ? dr[2] : dr[3]);
+                    if (argmax_better(key, n, am_best, am_bidx)) {
+                        am_best = key;
+                        am_bidx = n;
+                        am_sc = v;
+                    }
+                } else if (argmax_better(v, n, am_best, am_bidx)) {
                     am_best = v;
                     am_bidx = n;
                 }
@@ -483,9 +506,13 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
                 }
             }
         }
+        float* cs = sk_smem + 6 * NW * 2 * NB;               // SAMP: [NW][2][NB] scores of the candidates
+        if constexpr (SAMP) {
+            if (is_out_lane) cs[(wave * 2 + my_r) * NB + my_b] = am_sc;
+        }
         __syncthreads();
         if (tid < p.B) {
-            float best = -INFINITY;
+            float best = -INFINITY, bsc = -INFINITY;
             int bidx = 0x7fffffff;
             for (int i = 0; i < NW * 2; ++i) {
                 const float v = cv[i * NB + tid];
@@ -493,10 +520,12 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
                 if (argmax_better(v, ix, best, bidx)) {
                     best = v;
                     bidx = ix;
+                    if constexpr (SAMP) bsc = cs[i * NB + tid];
                 }
             }
             p.am_val[(size_t)tid * p.am_ld + block] = best;
             p.am_idx[(size_t)tid * p.am_ld + block] = bidx;
+            if constexpr (SAMP) p.am_sc[(size_t)tid * p.am_ld + block] = bsc;
             if constexpr (LP != 0) {   // the pairs of the NW x 2 output lanes of batch row `tid`, merged in slot order
                 float m = -INFINITY, s = 0.f, rm = -INFINITY, rs = 0.f;
                 for (int i = 0; i < NW * 2; ++i) {
@@ -525,6 +554,12 @@ template <int NB, int V, int NW, bool W_NT, bool WH, int LP>
 __global__ __launch_bounds__(64 * NW, 1) void skinny_logprob_kernel(const SkinnyParams p, const int nsplit, const int KS,
                                                                                 const int rows_per_group) {
     skinny_body<NB, V, NW, W_NT, false, true, WH, false, LP>(p, nsplit, KS, rows_per_group, blockIdx.x);
+}
+// the vocabulary GEMV of temperature sampling: the LP epilogue comparing Gumbel-max keys (SAMP), one block per SIMD set as above
+template <int NB, int V, int NW, bool W_NT, bool WH, int LP>
+__global__ __launch_bounds__(64 * NW, 1) void skinny_sample_kernel(const SkinnyParams p, const int nsplit, const int KS,
+                                                                               const int rows_per_group) {
+    skinny_body<NB, V, NW, W_NT, false, true, WH, false, LP, true>(p, nsplit, KS, rows_per_group, blockIdx.x);
 }
 
 // probe (see GELU_IN above): the K > 1024 direct-activation GEMV with the GELU / LayerNorm finish in its prologue
@@ -632,11 +667,51 @@ static hipError_t skinny_logprob_launch(const SkinnyParams& p, const SkinnyPlan&
 }
 
 template <int NB, int V, int NW>
+static hipError_t skinny_sample_launch(const SkinnyParams& p, const SkinnyPlan& pl, hipStream_t s) {
+    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
+    static_assert(7 * NW * 2 * NB <= NB * 1024, "candidates + four pair arrays + scores fit the activation staging area");
+    if (!p.am_lp || !p.am_seeds || !p.am_sc || !(p.am_temp > 0.f)) return hipErrorInvalidValue;
+    static PerDeviceFlag attr_set;
+    if (!attr_set.get() && smem > 48 * 1024) {
+        for (const void* f : {reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, false, 1>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, true, 1>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, false, 1>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, true, 1>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, false, 2>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, true, 2>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, false, 2>),
+                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, true, 2>)}) {
+            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+            if (e != hipSuccess) return e;
+        }
+        attr_set.set();
+    }
+#define WT_SK_SM(NT_, WH_, LP_) \
+    hipLaunchKernelGGL((skinny_sample_kernel<NB, V, NW, NT_, WH_, LP_>), dim3(pl.grid), dim3(64 * NW), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group)
+    switch ((p.am_lp == 2 ? 4 : 0) | (p.w_nt ? 2 : 0) | (p.w_half ? 1 : 0)) {
+    case 0: WT_SK_SM(false, false, 1); break;
+    case 1: WT_SK_SM(false, true, 1); break;
+    case 2: WT_SK_SM(true, false, 1); break;
+    case 3: WT_SK_SM(true, true, 1); break;
+    case 4: WT_SK_SM(false, false, 2); break;
+    case 5: WT_SK_SM(false, true, 2); break;
+    case 6: WT_SK_SM(true, false, 2); break;
+    default: WT_SK_SM(true, true, 2); break;
+    }
+#undef WT_SK_SM
+    return hipGetLastError();
+}
+
+template <int NB, int V, int NW>
 static hipError_t skinny_launch_cfg(const SkinnyParams& p, hipStream_t s) {
     SkinnyPlan pl;
     hipError_t e = skinny_plan<NB, V, NW>(p, &pl);
     if (e == hipSuccess) e = skinny_smem_attr<NB, V, NW>();
     if (e != hipSuccess) return e;
+    if (p.ymode == YMODE_ARGMAX && p.am_samp) {
+        if constexpr (NB <= 8) return skinny_sample_launch<NB, V, NW>(p, pl, s);
+        else return hipErrorInvalidValue;   // 16 rows: launch_skinny takes the four-wave form (skinny_sample_wide)
+    }
     if (p.ymode == YMODE_ARGMAX && p.am_lp) return skinny_logprob_launch<NB, V, NW>(p, pl, s);
     constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
 #define WT_SK_LAUNCH(NT_, AM_, WH_) \
@@ -695,8 +770,13 @@ hipError_t launch_skinny_gelu_in_probe(const SkinnyParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// The 16-row sampling form runs FOUR waves per workgroup, not eight: one wave per SIMD has 512 registers per lane, and with two (256
+// each, of which the log-probability variant already takes 254-256) the Philox rounds spilled 48-124 bytes per lane to scratch.
+static bool skinny_sample_wide(const SkinnyParams& p) { return p.B > 8 && p.ymode == YMODE_ARGMAX && p.am_samp; }
+
 int skinny_grid(const SkinnyParams& p) {  // workgroups launch_skinny will use for p (the column count of am_val / am_idx)
     SkinnyPlan pl;
+    if (skinny_sample_wide(p)) return skinny_plan<16, 2, 4>(p, &pl) == hipSuccess ? pl.grid : -1;
     hipError_t e = p.B <= 2 ? skinny_plan<2, 4, 4>(p, &pl) : p.B <= 4 ? skinny_plan<4, 4, 4>(p, &pl) : p.B <= 8 ? skinny_plan<8, 4, 4>(p, &pl)
                                                                                                    : skinny_plan<16, 2, 8>(p, &pl);
     return e == hipSuccess ? pl.grid : -1;
@@ -712,6 +792,11 @@ hipError_t launch_skinny(const SkinnyParams& p, hipStream_t s) {
     if (p.B <= 2) return skinny_launch_cfg<2, 4, 4>(p, s);
     if (p.B <= 4) return skinny_launch_cfg<4, 4, 4>(p, s);
     if (p.B <= 8) return skinny_launch_cfg<8, 4, 4>(p, s);
+    if (skinny_sample_wide(p)) {
+        SkinnyPlan pl;
+        const hipError_t e = skinny_plan<16, 2, 4>(p, &pl);
+        return e == hipSuccess ? skinny_sample_launch<16, 2, 4>(p, pl, s) : e;
+    }
     return skinny_launch_cfg<16, 2, 8>(p, s);  // 16 rows: half-width K-slices, 8 waves per block
 }
 
@@ -1276,6 +1361,72 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
     }
 }
 
+// Temperature sampling without the fused epilogue (the WT_NO_FUSED_ARGMAX A/B path): the logits are in memory, and this kernel walks them
+// in the PARTITION AND ORDER of the sampling GEMV's epilogue -- workgroup `block` of that GEMV's plan owns G row groups of rows_per_group
+// rows, and within a group the rows of each parity are finished in ascending order by one output lane -- so every partial (best key, its
+// id and score, the log-sum-exp pairs) is the float the fused epilogue would have written, and the finish kernel gives bitwise the same
+// token and log-probability on either path.  Grid (GEMV workgroups, B), one thread per (group, row parity) slot.
+__global__ __launch_bounds__(64) void sample_select_kernel(const SelectParams p, const int rows_per_group, const int G) {
+    __shared__ float s_val[16], s_sc[16];
+    __shared__ int s_idx[16];
+    __shared__ float4 s_lse[16];
+    const DecState* st = p.st;
+    if (st->done) return;  // steps enqueued past the stop test are no-ops
+    const int tid = threadIdx.x, block = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
+    const bool at_begin = cur_len == p.begin_index;
+    const float* lg = p.logits + (size_t)b * p.V;
+    float* tr = p.trace ? p.trace + ((size_t)b * (p.max_length - 1) + step) * p.V : nullptr;
+    float best = -INFINITY, bsc = -INFINITY;
+    int bidx = 0x7fffffff;
+    float lm = -INFINITY, ls = 0.f, rm = -INFINITY, rs = 0.f;
+    if (tid < 2 * G) {
+        const unsigned long long seed = p.samp_seeds[b];
+        const int row_begin = (int)min((long long)p.V, ((long long)block * G + (tid >> 1)) * rows_per_group);
+        const int row_end = min(p.V, row_begin + rows_per_group);
+        for (int n = row_begin + (tid & 1); n < row_end; n += 2) {
+            float x = lg[n];
+            if (tr) tr[n] = x;
+            if (p.lp_ns >= 0) {
+                lse_add(rm, rs, x);
+                if (n == p.lp_ns) p.lp_side[2 * b + 1] = x;
+            }
+            const uint8_t mk = p.mask[n];
+            if ((mk & 1) || ((mk & 2) && at_begin)) x = -INFINITY;
+            lse_add(lm, ls, x);
+            if (n == p.eos) p.lp_side[2 * b] = x;
+            unsigned dr[4];
+            sample_draws(seed, cur_len, n >> 2, dr);
+            const int q = n & 3;
+            const float key = sample_key(x, p.samp_temp, q == 0 ? dr[0] : q == 1 ? dr[1] : q == 2 ? dr[2] : dr[3]);
+            if (argmax_better(key, n, best, bidx)) {
+                best = key;
+                bidx = n;
+                bsc = x;
+            }
+        }
+        s_val[tid] = best; s_idx[tid] = bidx; s_sc[tid] = bsc; s_lse[tid] = make_float4(lm, ls, rm, rs);
+    }
+    __syncthreads();
+    if (tid == 0) {   // the slots in the order the epilogue's LDS stage scans them (its other slots are empty: exact no-ops)
+        best = -INFINITY; bsc = -INFINITY; bidx = 0x7fffffff;
+        lm = -INFINITY; ls = 0.f; rm = -INFINITY; rs = 0.f;
+        for (int i = 0; i < 2 * G; ++i) {
+            if (argmax_better(s_val[i], s_idx[i], best, bidx)) {
+                best = s_val[i];
+                bidx = s_idx[i];
+                bsc = s_sc[i];
+            }
+            lse_merge(lm, ls, s_lse[i].x, s_lse[i].y);
+            if (p.lp_ns >= 0) lse_merge(rm, rs, s_lse[i].z, s_lse[i].w);
+        }
+        const size_t at = (size_t)b * p.n_parts + block;
+        p.part_val[at] = best;
+        p.part_idx[at] = bidx;
+        p.samp_sc[at] = bsc;
+        p.lp_part[at] = make_float4(lm, ls, rm, rs);
+    }
+}
+
 // ---- timestamp mode (WhisperTimeStampLogitsProcessor, logits_process.py:1331-1396, after Suppress -> SuppressAtBegin -> Force).
 // ts_select_kernel, grid (SELECT_CHUNKS, B): the static masks, <|notimestamps|> and the per-row timestamp grammar (pairs; nothing but
 // a timestamp or EOS.. after a lone timestamp; the max-initial-timestamp cap), then one TsPart per chunk.  The log-sum-exp of the
@@ -1284,10 +1435,18 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(const SelectParams p
 __device__ __forceinline__ float ts_rescale(float s, float m, float nm) { return s == 0.f ? 0.f : s * expf(m - nm); }
 
 // LP (log-probability mode): TsPart also carries the text-side pair (xmax, xsum), and lp_part the raw pair of the chunk (no_speech_prob).
-template <bool LP = false>
+// SAMP (temperature sampling, with LP): tmax / smax become the best Gumbel-max KEYS of the chunk's text / timestamp ids; their scores and
+// the chunk's best unperturbed text score (rule 5's side; the timestamp pair (zmax, zsum) is of the scores as before) travel in samp_ts.
+struct TsSamp {
+    float tsc, ssc, rt;    // score of targ, score of sarg, best text score (NaN-aware, with its index for the order)
+    int rti;
+};
+template <bool LP = false, bool SAMP = false>
 __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
+    static_assert(!SAMP || LP, "sampling runs with the log-sum-exp pairs on");
     __shared__ TsPart s_part[4];
     __shared__ float2 s_raw[4];
+    __shared__ TsSamp s_samp[4];
     const DecState* st = p.st;
     if (st->done) return;  // steps enqueued past the stop test are no-ops
     const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
@@ -1311,7 +1470,12 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
     r.xmax = -INFINITY;
     r.xsum = 0.f;
     float rm = -INFINITY, rs = 0.f;
-    auto consider = [&](float x, uint8_t mk, int v) {
+    TsSamp q;
+    q.tsc = q.ssc = q.rt = -INFINITY;
+    q.rti = 0x7fffffff;
+    unsigned long long seed = 0;
+    if constexpr (SAMP) seed = p.samp_seeds[b];
+    auto consider = [&](float x, uint8_t mk, int v, unsigned draw) {
         if constexpr (LP) {
             if (p.lp_ns >= 0) {
                 lse_add(rm, rs, x);
@@ -1322,16 +1486,26 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
         if constexpr (LP) {
             if (v == p.eos) p.lp_side[2 * b] = x;
         }
+        float key = x;
+        if constexpr (SAMP) key = sample_key(x, p.samp_temp, draw);
         if (v < p.tb) {
-            if (argmax_better(x, v, r.tmax, r.targ)) {
-                r.tmax = x;
+            if (argmax_better(key, v, r.tmax, r.targ)) {
+                r.tmax = key;
                 r.targ = v;
+                if constexpr (SAMP) q.tsc = x;
+            }
+            if constexpr (SAMP) {
+                if (argmax_better(x, v, q.rt, q.rti)) {
+                    q.rt = x;
+                    q.rti = v;
+                }
             }
             if constexpr (LP) lse_add(r.xmax, r.xsum, x);
         } else {
-            if (argmax_better(x, v, r.smax, r.sarg)) {
-                r.smax = x;
+            if (argmax_better(key, v, r.smax, r.sarg)) {
+                r.smax = key;
                 r.sarg = v;
+                if constexpr (SAMP) q.ssc = x;
             }
             if (x > r.zmax) {
                 r.zsum = ts_rescale(r.zsum, r.zmax, x) + 1.f;
@@ -1352,10 +1526,12 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
             const float4 x = lg4[i];
             const uchar4 m = mk4[i];
             if (tr) tr4[i] = x;
-            consider(x.x, m.x, 4 * i);
-            consider(x.y, m.y, 4 * i + 1);
-            consider(x.z, m.z, 4 * i + 2);
-            consider(x.w, m.w, 4 * i + 3);
+            unsigned dr[4] = {0u, 0u, 0u, 0u};
+            if constexpr (SAMP) sample_draws(seed, cur_len, i, dr);
+            consider(x.x, m.x, 4 * i, dr[0]);
+            consider(x.y, m.y, 4 * i + 1, dr[1]);
+            consider(x.z, m.z, 4 * i + 2, dr[2]);
+            consider(x.w, m.w, 4 * i + 3, dr[3]);
         }
     } else {
         const int per = (p.V + SELECT_CHUNKS - 1) / SELECT_CHUNKS;
@@ -1363,17 +1539,28 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
         for (int v = v0 + tid; v < v1; v += 256) {
             const float x = lg[v];
             if (tr) tr[v] = x;
-            consider(x, p.mask[v], v);
+            unsigned dr[4] = {0u, 0u, 0u, 0u};
+            if constexpr (SAMP) sample_draws(seed, cur_len, v >> 2, dr);
+            const int k = v & 3;
+            consider(x, p.mask[v], v, k == 0 ? dr[0] : k == 1 ? dr[1] : k == 2 ? dr[2] : dr[3]);
         }
     }
-    auto merge = [](TsPart& a, const TsPart& o) {
+    auto merge = [](TsPart& a, const TsPart& o, TsSamp& qa, const TsSamp& qo) {
         if (argmax_better(o.tmax, o.targ, a.tmax, a.targ)) {
             a.tmax = o.tmax;
             a.targ = o.targ;
+            if constexpr (SAMP) qa.tsc = qo.tsc;
         }
         if (argmax_better(o.smax, o.sarg, a.smax, a.sarg)) {
             a.smax = o.smax;
             a.sarg = o.sarg;
+            if constexpr (SAMP) qa.ssc = qo.ssc;
+        }
+        if constexpr (SAMP) {
+            if (argmax_better(qo.rt, qo.rti, qa.rt, qa.rti)) {
+                qa.rt = qo.rt;
+                qa.rti = qo.rti;
+            }
         }
         const float nm = fmaxf(a.zmax, o.zmax);   // (never NaN: zmax only takes finite or infinite scores)
         a.zsum = ts_rescale(a.zsum, a.zmax, nm) + ts_rescale(o.zsum, o.zmax, nm);
@@ -1394,16 +1581,25 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
             x.xsum = __shfl_xor(r.xsum, o);
             lse_merge(rm, rs, __shfl_xor(rm, o), __shfl_xor(rs, o));
         }
-        merge(r, x);
+        TsSamp y = q;
+        if constexpr (SAMP) {
+            y.tsc = __shfl_xor(q.tsc, o);
+            y.ssc = __shfl_xor(q.ssc, o);
+            y.rt = __shfl_xor(q.rt, o);
+            y.rti = __shfl_xor(q.rti, o);
+        }
+        merge(r, x, q, y);
     }
     if ((tid & 63) == 0) {
         s_part[tid >> 6] = r;
         if constexpr (LP) s_raw[tid >> 6] = make_float2(rm, rs);
+        if constexpr (SAMP) s_samp[tid >> 6] = q;
     }
     __syncthreads();
     if (tid == 0) {
-        for (int i = 1; i < 4; ++i) merge(r, s_part[i]);
+        for (int i = 1; i < 4; ++i) merge(r, s_part[i], q, s_samp[i]);
         p.ts_part[b * SELECT_CHUNKS + chunk] = r;
+        if constexpr (SAMP) p.samp_ts[b * SELECT_CHUNKS + chunk] = make_float4(q.tsc, q.ssc, q.rt, 0.f);
         if constexpr (LP) {
             for (int i = 1; i < 4; ++i) lse_merge(rm, rs, s_raw[i].x, s_raw[i].y);
             p.lp_part[b * SELECT_CHUNKS + chunk] = make_float4(-INFINITY, 0.f, rm, rs);
@@ -1421,51 +1617,68 @@ __device__ __forceinline__ void ts_request(const SelectParams& p, const int b, c
 struct LpPick {
     float num, m, s;
     bool forced, text_masked;
+    float key;             // sampling: the key the token won with
 };
 // rules 2 and 5 and the argmax of one row; every lane of the group returns the same token
-template <bool LP = false>
+// SAMP: tm / sm are keys; rule 5 compares the timestamps' log-sum-exp with the best unperturbed text score, then the better KEY among the
+// surviving region(s) is the token and its carried score the numerator
+template <bool LP = false, bool SAMP = false>
 __device__ __forceinline__ int ts_pick(const SelectParams& p, const int b, const int l, const int lpb, const TsPart& c, const int cur_len,
-                                       LpPick* lp = nullptr) {
+                                       LpPick* lp = nullptr, const float4 sc = float4{0.f, 0.f, 0.f, 0.f}) {
     float tm = -INFINITY, sm = -INFINITY, zm = -INFINITY, zs = 0.f;
     int ti = 0x7fffffff, si = 0x7fffffff;
     float xm = -INFINITY, xs = 0.f;
+    float tsc = -INFINITY, ssc = -INFINITY, rt = -INFINITY;
     if (b < p.B && l < SELECT_CHUNKS) {
         tm = c.tmax; ti = c.targ; sm = c.smax; si = c.sarg; zm = c.zmax; zs = c.zsum;
         if constexpr (LP) {
             xm = c.xmax; xs = c.xsum;
+        }
+        if constexpr (SAMP) {
+            tsc = sc.x; ssc = sc.y; rt = sc.z;
         }
     }
     float M = zm;
     for (int o = lpb >> 1; o >= 1; o >>= 1) {   // lpb <= 64 and a power of two: a group never straddles a wave
         const float otm = __shfl_xor(tm, o), osm = __shfl_xor(sm, o);
         const int oti = __shfl_xor(ti, o), osi = __shfl_xor(si, o);
+        const float otsc = SAMP ? __shfl_xor(tsc, o) : 0.f, ossc = SAMP ? __shfl_xor(ssc, o) : 0.f, ort = SAMP ? __shfl_xor(rt, o) : 0.f;
         if (argmax_better(otm, oti, tm, ti)) {
             tm = otm;
             ti = oti;
+            if constexpr (SAMP) tsc = otsc;
         }
         if (argmax_better(osm, osi, sm, si)) {
             sm = osm;
             si = osi;
+            if constexpr (SAMP) ssc = ossc;
+        }
+        if constexpr (SAMP) {
+            if (argmax_better(ort, 0, rt, 0)) rt = ort;   // a NaN-aware maximum
         }
         M = fmaxf(M, __shfl_xor(M, o));
     }
+    const float text_best = SAMP ? rt : tm;   // rule 5's text side: the best unperturbed text score
     float Z = ts_rescale(zs, zm, M);
     for (int o = lpb >> 1; o >= 1; o >>= 1) Z += __shfl_xor(Z, o);
     const float lse = M + logf(Z);   // -inf when every timestamp is masked (M = -inf, Z = 0); NaN with a NaN timestamp score
     int tok;
     if (cur_len == p.ts_begin_index - 1) tok = p.tb;        // rule 2: <|0.00|> opens the transcript
-    else if (lse > tm) tok = si;                            // rule 5: the timestamps' total mass beats every text token
+    else if (lse > text_best) tok = si;                     // rule 5: the timestamps' total mass beats every text token
     else tok = argmax_better(sm, si, tm, ti) ? si : ti;
     if constexpr (LP) {   // rule 5 leaves the timestamps alone in the softmax; otherwise text and timestamps share it
         for (int o = lpb >> 1; o >= 1; o >>= 1) lse_merge(xm, xs, __shfl_xor(xm, o), __shfl_xor(xs, o));
         lp->forced = cur_len == p.ts_begin_index - 1;
-        lp->text_masked = !lp->forced && lse > tm;
+        lp->text_masked = !lp->forced && lse > text_best;
         lp->m = M;
         lp->s = Z;
-        lp->num = sm;
+        lp->num = SAMP ? ssc : sm;
+        lp->key = sm;
         if (!lp->text_masked) {
             lse_merge(lp->m, lp->s, xm, xs);
-            lp->num = argmax_better(sm, si, tm, ti) ? sm : tm;
+            const bool ts_wins = argmax_better(sm, si, tm, ti);
+            lp->num = SAMP ? (ts_wins ? ssc : tsc) : (ts_wins ? sm : tm);
+            lp->key = ts_wins ? sm : tm;
         }
     }
     if ((unsigned)tok >= (unsigned)p.V) tok = p.eos;        // unreachable with a NaN-aware argmax; never index the embedding out of range
@@ -1473,7 +1686,7 @@ __device__ __forceinline__ int ts_pick(const SelectParams& p, const int b, const
         if (p.ts_tok) p.ts_tok[b] = tok;
         if (p.ts_stats) {
             p.ts_stats[2 * b] = lse;
-            p.ts_stats[2 * b + 1] = tm;
+            p.ts_stats[2 * b + 1] = text_best;
         }
     }
     return tok;
@@ -1513,18 +1726,20 @@ __device__ __forceinline__ float4 finish_lse(const SelectParams& p, const int b,
     }
     return make_float4(m, s, rm, rs);
 }
-template <bool LP = false>
+// SAMP: the partials' values are keys; the winner's score is fetched from samp_sc once the lane's own best partial is known
+template <bool LP = false, bool SAMP = false>
 __device__ __forceinline__ int finish_argmax(const SelectParams& p, const int b, const int l, const int lpb, const FinishCand& c,
-                                             float* best_out = nullptr) {
+                                             float* best_out = nullptr, float* score_out = nullptr) {
     const size_t pbase = (size_t)min(b, p.B - 1) * p.n_parts;
     float best = -INFINITY;
-    int bidx = 0x7fffffff;
+    int bidx = 0x7fffffff, bpart = -1;
     if (b < p.B) {
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (l + k * lpb < p.n_parts && argmax_better(c.pv[k], c.pi[k], best, bidx)) {
                 best = c.pv[k];
                 bidx = c.pi[k];
+                if constexpr (SAMP) bpart = l + k * lpb;
             }
         for (int i = l + 8 * lpb; i < p.n_parts; i += lpb) {
             const float v = p.part_val[pbase + i];
@@ -1532,18 +1747,26 @@ __device__ __forceinline__ int finish_argmax(const SelectParams& p, const int b,
             if (argmax_better(v, ix, best, bidx)) {
                 best = v;
                 bidx = ix;
+                if constexpr (SAMP) bpart = i;
             }
         }
+    }
+    float bsc = -INFINITY;
+    if constexpr (SAMP) {
+        if (bpart >= 0) bsc = p.samp_sc[pbase + bpart];
     }
     for (int o = lpb >> 1; o >= 1; o >>= 1) {   // lpb <= 64 and a power of two: a group never straddles a wave
         const float ov = __shfl_xor(best, o);
         const int oi = __shfl_xor(bidx, o);
+        const float osc = SAMP ? __shfl_xor(bsc, o) : 0.f;
         if (argmax_better(ov, oi, best, bidx)) {
             best = ov;
             bidx = oi;
+            if constexpr (SAMP) bsc = osc;
         }
     }
     if constexpr (LP) *best_out = best;
+    if constexpr (SAMP) *score_out = bsc;
     if ((unsigned)bidx >= (unsigned)p.V) bidx = p.eos;   // unreachable with a NaN-aware argmax; never index the embedding out of range
     return bidx;
 }
@@ -1562,8 +1785,10 @@ __device__ __forceinline__ void finish_embed(const SelectParams& p, const int* s
 // LP: the log-probability mode -- token_logprob[b][cur_len] = s[tok] - logsumexp(s) over the step's processed scores s (0 at a forced
 // position; the EOS score where a bench switch replaced the token), its running sum while the row is unfinished, and at step 0
 // no_speech_prob = softmax(raw logits)[lp_ns].  The LP = false instantiations are the kernels as they were.
-template <bool TS, bool LP = false>
+// SAMP (with LP): the partials are merged by their Gumbel-max key and the log-probability's numerator is the carried score of the winner.
+template <bool TS, bool LP = false, bool SAMP = false>
 __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p) {
+    static_assert(!SAMP || LP, "sampling runs with the log-sum-exp pairs on");
     __shared__ int s_tok[MAX_ROWS];
     __shared__ int s_pos[MAX_ROWS];
     __shared__ int s_unf[MAX_ROWS];
@@ -1573,8 +1798,13 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     const int b = tid / lpb, l = tid % lpb, bc = min(b, p.B - 1);
     FinishCand cand;
     TsPart tcand;
-    if constexpr (TS) ts_request(p, b, l, tcand);
-    else finish_request(p, b, l, lpb, cand);
+    float4 tsamp = float4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (TS) {
+        ts_request(p, b, l, tcand);
+        if constexpr (SAMP) tsamp = p.samp_ts[(size_t)bc * SELECT_CHUNKS + min(l, SELECT_CHUNKS - 1)];
+    } else {
+        finish_request(p, b, l, lpb, cand);
+    }
     const int unf = p.unfinished[bc];
     // the rows of a wt_decoder_begin batch stay aligned: row 0's counters are everybody's
     const int done = st->done, cur_len = st->cur_len[0], step = st->step, pos = st->pos[0], self_len = st->self_len[0], seq = st->seq + 1,
@@ -1595,10 +1825,14 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     float4 lse4;
     if constexpr (LP) lse4 = finish_lse(p, b, l, lpb);
     if constexpr (TS) {
-        if constexpr (LP) tok = ts_pick<true>(p, b, l, lpb, tcand, st->cur_len[bc], &pick);
+        if constexpr (SAMP) tok = ts_pick<true, true>(p, b, l, lpb, tcand, st->cur_len[bc], &pick, tsamp);
+        else if constexpr (LP) tok = ts_pick<true>(p, b, l, lpb, tcand, st->cur_len[bc], &pick);
         else tok = ts_pick(p, b, l, lpb, tcand, st->cur_len[bc]);
     } else {
-        if constexpr (LP) {
+        if constexpr (SAMP) {
+            tok = finish_argmax<true, true>(p, b, l, lpb, cand, &pick.key, &pick.num);
+            pick.m = lse4.x; pick.s = lse4.y; pick.forced = false; pick.text_masked = false;
+        } else if constexpr (LP) {
             tok = finish_argmax<true>(p, b, l, lpb, cand, &pick.num);
             pick.m = lse4.x; pick.s = lse4.y; pick.forced = false; pick.text_masked = false;
         } else {
@@ -1606,6 +1840,9 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
         }
     }
     if (b < p.B && l == 0) {
+        if constexpr (SAMP) {
+            if (p.samp_key) p.samp_key[b] = pick.key;
+        }
         if (forced >= 0) tok = forced;
         if (p.force_eos_step >= 0 && step == p.force_eos_step) tok = p.eos;  // bench-only transcript length
         if (row_eos >= 0 && step == row_eos) tok = p.eos;                    // ... per row (variable-length workload)
@@ -2228,10 +2465,34 @@ hipError_t launch_beam_finalize(const SelectParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// temperature sampling over logits in memory: sample_select_kernel in the plan of the sampling GEMV for (B, V, samp_K), then the finish kernel
+static hipError_t launch_sample_select(const SelectParams& p, hipStream_t s) {
+    if (!p.lp_on || p.stream || p.beam_on || !p.samp_seeds || !p.samp_sc || !(p.samp_temp > 0.f) || !p.lp_part || !p.lp_side || !p.lp_tok ||
+        !p.lp_sum || p.lp_ns >= p.V || (p.lp_ns >= 0 && !p.lp_nsp))
+        return hipErrorInvalidValue;
+    SkinnyParams k;
+    memset(&k, 0, sizeof k);
+    k.B = p.B; k.N = p.V; k.K = p.samp_K; k.ymode = YMODE_ARGMAX; k.am_samp = 1;
+    SkinnyPlan pl;
+    const hipError_t e = p.B <= 2 ? skinny_plan<2, 4, 4>(k, &pl) : p.B <= 4 ? skinny_plan<4, 4, 4>(k, &pl) : p.B <= 8 ? skinny_plan<8, 4, 4>(k, &pl)
+                                                                                                      : skinny_plan<16, 2, 4>(k, &pl);
+    if (e != hipSuccess) return e;
+    const int G = 4 / pl.nsplit;   // every sampling form runs four waves per workgroup
+    if (p.samp_parts_cap < pl.grid) return hipErrorInvalidValue;
+    SelectParams q = p;
+    q.n_parts = pl.grid;
+    hipLaunchKernelGGL(sample_select_kernel, dim3(pl.grid, p.B), dim3(64), 0, s, q, pl.rows_per_group, G);
+    hipLaunchKernelGGL((greedy_finish_kernel<false, true, true>), dim3(1), dim3(256), 0, s, q);
+    return hipGetLastError();
+}
+
 hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     if (p.B > MAX_ROWS || p.n_parts < 1 || (!p.fused && p.n_parts != SELECT_CHUNKS)) return hipErrorInvalidValue;
+    if (p.samp_on && !p.fused && !p.ts_on) return launch_sample_select(p, s);
     if (p.stream && (!p.host_ids || !p.host_len || p.trace)) return hipErrorInvalidValue;
     if (p.lp_on && (p.beam_on || !p.lp_part || !p.lp_side || !p.lp_tok || !p.lp_sum || p.lp_ns >= p.V || (p.lp_ns >= 0 && !p.lp_nsp)))
+        return hipErrorInvalidValue;
+    if (p.samp_on && (!p.lp_on || p.stream || !p.samp_seeds || !(p.samp_temp > 0.f) || (p.ts_on ? !p.samp_ts : !p.samp_sc)))
         return hipErrorInvalidValue;
     if (p.beam_on) {   // beam search: batch decodes only, over logits in HBM
         if (!beam_params_ok(p)) return hipErrorInvalidValue;
@@ -2242,7 +2503,10 @@ hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     if (p.ts_on) {   // timestamp mode: batch decodes only, over logits in HBM
         if (p.fused || p.stream || !p.ts_part || p.tb <= 0 || p.tb >= p.V || p.no_ts < 0 || p.no_ts >= p.tb || p.ts_begin_index < 2)
             return hipErrorInvalidValue;
-        if (p.lp_on) {
+        if (p.samp_on) {
+            hipLaunchKernelGGL((ts_select_kernel<true, true>), dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
+            hipLaunchKernelGGL((greedy_finish_kernel<true, true, true>), dim3(1), dim3(256), 0, s, p);
+        } else if (p.lp_on) {
             hipLaunchKernelGGL(ts_select_kernel<true>, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
             hipLaunchKernelGGL((greedy_finish_kernel<true, true>), dim3(1), dim3(256), 0, s, p);
         } else {
@@ -2253,6 +2517,10 @@ hipError_t launch_greedy_select(const SelectParams& p, hipStream_t s) {
     }
     if (p.lp_on) {   // log-probability mode: batch decodes only; the same launch count as the plain tail
         if (p.stream) return hipErrorInvalidValue;
+        if (p.samp_on) {   // temperature sampling, fused: the GEMV's sampling epilogue wrote the partials (else: launch_sample_select)
+            hipLaunchKernelGGL((greedy_finish_kernel<false, true, true>), dim3(1), dim3(256), 0, s, p);
+            return hipGetLastError();
+        }
         if (!p.fused) hipLaunchKernelGGL(greedy_select_kernel<true>, dim3(SELECT_CHUNKS, p.B), dim3(256), 0, s, p);
         hipLaunchKernelGGL((greedy_finish_kernel<false, true>), dim3(1), dim3(256), 0, s, p);
         return hipGetLastError();

@@ -113,6 +113,13 @@ struct SkinnyParams {
     float4* am_lse;
     float* am_side;
     int am_lp, am_eos, am_ns;
+    // temperature sampling (am_samp != 0; wt_decoder_set_sampling; needs am_lp != 0): the SAMP instantiations compare the Gumbel-max key
+    // s / am_temp + g(am_seeds[b], st->cur_len[b], n) (sample_key below) instead of the score s; am_val then holds the winning KEY and am_sc
+    // [B][am_ld] the winner's score s.  am_samp == 0: the instantiations without it run, exactly as before.
+    int am_samp;
+    float am_temp;
+    const unsigned long long* am_seeds;   // [B]
+    float* am_sc;
 };
 
 // ---- decode attention (query length 1), split over the key axis ---------------------------------------------
@@ -369,7 +376,43 @@ struct SelectParams {
     float* lp_tok;
     float* lp_sum;
     float* lp_nsp;
+    // temperature sampling (samp_on != 0; wt_decoder_set_sampling; with lp_on): the SAMP instantiations of the select / finish kernels run.
+    // A partial's part_val is the best Gumbel-max KEY of its ids (sample_key below) and samp_sc [B][n_parts] the score s of that id.  Timestamp
+    // mode: TsPart.tmax / smax are the best text / timestamp KEYS of the chunk, and samp_ts [B][SELECT_CHUNKS] holds (score of targ, score
+    // of sarg, the chunk's best unperturbed text score -- rule 5's tmax --, unused).  samp_key [B] (optional): the key the token won with.
+    // Without the fused epilogue (fused == 0, no timestamp mode) sample_select_kernel walks the logits in the partition of the sampling GEMV
+    // for (B, V, samp_K) -- samp_K = that GEMV's K -- and writes one partial per GEMV workgroup: the part / lp_part / samp_sc rows must hold
+    // samp_parts_cap >= that plan's workgroups, which replace n_parts for the launch.
+    int samp_on, samp_K, samp_parts_cap;
+    float samp_temp;
+    const unsigned long long* samp_seeds;   // [B]
+    float* samp_sc;
+    float4* samp_ts;
+    float* samp_key;
 };
+// ---- temperature sampling: Gumbel-max over a counter-based generator (DESIGN.md "Temperature sampling").  Philox-4x32-10 (Salmon et al.,
+// SC'11): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped by the Weyl constants between rounds.
+__host__ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// standard Gumbel noise of one 32-bit draw: u = ((x >> 9) + 0.5) 2^-23 is exact in fp32 and strictly inside (0, 1)
+__device__ __forceinline__ float gumbel_of(const unsigned x) {
+    const float u = ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f;
+    return -logf(-logf(u));
+}
+// the four draws that serve vocabulary ids 4 * v4 .. 4 * v4 + 3 of a row with `seed` writing sequence position t
+__device__ __forceinline__ void sample_draws(const unsigned long long seed, const int t, const int v4, unsigned out[4]) {
+    philox4x32_10((unsigned)v4, (unsigned)t, 0u, 0u, (unsigned)seed, (unsigned)(seed >> 32), out);
+}
+// key of a score under temperature T: s / T + g (IEEE division: what the reference's TemperatureLogitsWarper computes); -inf stays -inf, NaN NaN
+__device__ __forceinline__ float sample_key(const float s, const float T, const unsigned x) { return s / T + gumbel_of(x); }
 // online log-sum-exp pairs (m = largest score that is neither NaN nor -inf, s = sum of exp(x - m)): the empty pair is (-inf, 0), a NaN score
 // makes s NaN
 __device__ __forceinline__ float lse_rescale(float s, float m, float nm) { return s == 0.f ? 0.f : s * expf(m - nm); }
@@ -434,6 +477,9 @@ inline int vocab_skinny_fuse_argmax(SkinnyParams& k, const SelectParams& sp) {
     k.am_begin_index = sp.begin_index; k.am_trace = sp.trace; k.am_trace_steps = sp.max_length - 1;
     if (sp.lp_on) {
         k.am_lp = sp.lp_ns >= 0 ? 2 : 1; k.am_lse = sp.lp_part; k.am_side = sp.lp_side; k.am_eos = sp.eos; k.am_ns = sp.lp_ns;
+        if (sp.samp_on) {
+            k.am_samp = 1; k.am_temp = sp.samp_temp; k.am_seeds = sp.samp_seeds; k.am_sc = sp.samp_sc;
+        }
     }
     const int grid = skinny_grid(k);
     k.am_ld = grid;

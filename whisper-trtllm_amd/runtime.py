@@ -248,6 +248,40 @@ def _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, vocab_si
         raise ValueError(f"no_speech_token_id must be an id in [0, {vocab_size}), got {no_speech_token_id!r}")
 
 
+def _check_sampling_args(temperature, seed, seeds, batch, num_beams):
+    """What the engine refuses (wt_decoder_set_sampling / wt_decoder_begin: WT_E_INVALID, WT_E_UNSUPPORTED), refused before anything is
+    enqueued.  Returns the row seeds of a sampled decode ([] when sampling is off)."""
+    import math
+    if not isinstance(temperature, (int, float)) or not math.isfinite(temperature):
+        raise ValueError(f"temperature must be a finite number, got {temperature!r}")
+    if temperature <= 0:
+        return []
+    if num_beams > 1:
+        raise ValueError("beam search and temperature sampling cannot be combined")
+    batch = int(batch.shape[0]) if hasattr(batch, "shape") else int(batch)      # (the encoder memory itself: looked at only when sampling)
+    if seeds is None:
+        seeds = [int(seed) + b for b in range(batch)]
+    seeds = [int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds]
+    if len(seeds) < batch:
+        raise ValueError(f"seeds needs one entry per utterance ({batch}), got {len(seeds)}")
+    return seeds[:batch]
+
+
+def _default_text_of(config):
+    """ids -> text for the compression ratio of generate_with_fallback: the config's token decoder when it carries a vocabulary
+    (`vocab` [+ `added_tokens`], or `tokenizer_dir` with a vocab.json), else the ids in decimal joined by spaces (synthetic models)."""
+    import os
+    from .text import WhisperTokenDecoder
+    tok = None
+    if isinstance(config.get("vocab"), dict):
+        tok = WhisperTokenDecoder(config["vocab"], config.get("added_tokens"))
+    elif config.get("tokenizer_dir") and os.path.exists(os.path.join(config["tokenizer_dir"], "vocab.json")):
+        tok = WhisperTokenDecoder.from_dir(config["tokenizer_dir"])
+    if tok is not None:
+        return lambda ids: tok.decode(ids, skip_special_tokens=True)
+    return lambda ids: " ".join(str(int(t)) for t in ids)
+
+
 def _check_token_timestamp_args(config, info, return_token_timestamps, alignment_heads, median_filter_width, num_beams):
     """Token-level timestamps: the head list to use ([] when the mode is off).  `alignment_heads` of the call wins over the config's
     (generation_config.json's `alignment_heads`, which examples/whisper/_common.py copies into the config).  Refused before anything is
@@ -352,6 +386,15 @@ class WhisperDecoderEngine:
                    "wt_decoder_set_logprobs")
         self._lp_ns = no_speech_token_id if on else None
 
+    def _set_sampling(self, temperature: float = 0.0, seeds=()):
+        t = None
+        if temperature > 0:
+            arr = (ctypes.c_uint64 * len(seeds))(*seeds)
+            self._seed_keep = arr
+            t = _lib.SamplingParams(float(temperature), ctypes.cast(arr, ctypes.POINTER(ctypes.c_uint64)), len(seeds), 0)
+        _lib.check(self.session._lib.wt_decoder_set_sampling(self.session.handle, ctypes.byref(t) if t is not None else None),
+                   "wt_decoder_set_sampling")
+
     def read_logprobs(self, ids):
         """DecodeScores of the decode in flight for its ids [B, cur_len] (wt_decoder_read_logprobs, stream-ordered)."""
         import torch
@@ -405,8 +448,9 @@ class WhisperDecoderEngine:
     def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
               return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
               return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7,
-              return_logprobs: bool = False, no_speech_token_id=None):
-        """Start a decode (wt_decoder_begin).  `return_logprobs` / `no_speech_token_id`: see `generate` (read with `read_logprobs`).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
+              return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0, seed: int = 0, seeds=None):
+        """Start a decode (wt_decoder_begin).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
+        with `seeds[b]`, or `seed + b` without a list; not with beams.  `return_logprobs` / `no_speech_token_id`: see `generate` (read with `read_logprobs`).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
         the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
         `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
         (False or True); utterances x num_beams <= 16 rows per call; not together with timestamps, logits_trace or force_eos_step(s).
@@ -418,6 +462,7 @@ class WhisperDecoderEngine:
         i = self.session.info
         tt_heads = _check_token_timestamp_args(self.config, i, True, alignment_heads, median_filter_width, num_beams) if return_token_timestamps else []
         _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, i.vocab_size)
+        row_seeds = _check_sampling_args(temperature, seed, seeds, encoder_hidden, num_beams)
         if encoder_hidden.dtype != torch.float32 or tuple(encoder_hidden.shape[1:]) != (i.max_source_positions, i.d_model):
             raise ValueError(f"encoder_hidden must be float32 [B,{i.max_source_positions},{i.d_model}]")
         if not encoder_hidden.is_cuda or (logits_trace is not None and not logits_trace.is_cuda):
@@ -432,6 +477,7 @@ class WhisperDecoderEngine:
         self._set_beam_search(num_beams, length_penalty, early_stopping)
         self._set_token_timestamps(tt_heads, median_filter_width)
         self._set_logprobs(return_logprobs, no_speech_token_id)
+        self._set_sampling(temperature if row_seeds else 0.0, row_seeds)
         self._beams = int(num_beams) if num_beams > 1 else 1
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self.session._lib.wt_decoder_begin(self.session.handle, self._enc.data_ptr(), self._B, ctypes.byref(self._p),
@@ -496,8 +542,13 @@ class WhisperDecoderEngine:
     def generate(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, chunk: int = 0, force_eos_steps=None,
                  lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, return_scores: bool = False, return_token_timestamps: bool = False, alignment_heads=None,
-                 median_filter_width: int = 7, return_logprobs: bool = False, no_speech_token_id=None):
+                 median_filter_width: int = 7, return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0,
+                 seed: int = 0, seeds=None):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
+        `temperature` > 0: every token is a draw from softmax(scores / temperature) instead of the argmax (Gumbel-max over a counter-based
+        generator, on the device; include/whisper_trtllm_amd.h (9f)).  Utterance b draws with `seeds[b]`, or with `seed + b`: a draw depends
+        on the seed, the position and the id alone, so it is repeatable and independent of the batch.  Log-probabilities of a sampled decode
+        are those of the untempered scores.  Not with num_beams > 1.
         `return_logprobs`: token log-probabilities from the device (wt_decoder_set_logprobs, no extra launch): returns (ids, DecodeScores),
         or (ids, token timestamps, DecodeScores) with `return_token_timestamps`; `no_speech_token_id` also fills
         DecodeScores.no_speech_prob.  Greedy decoding only (not with num_beams > 1).
@@ -512,6 +563,8 @@ class WhisperDecoderEngine:
             _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, self.session.info.vocab_size)
         if return_scores and num_beams <= 1:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence score)")
+        row_seeds = _check_sampling_args(temperature, seed, seeds, encoder_hidden, num_beams)
+        samp = lambda i, j: {"temperature": temperature, "seeds": row_seeds[i:j]} if row_seeds else {}
         tt = None
         if return_token_timestamps:
             _check_token_timestamp_args(self.config, self.session.info, True, alignment_heads, median_filter_width, num_beams)
@@ -544,7 +597,7 @@ class WhisperDecoderEngine:
             lp = {"return_logprobs": True, "no_speech_token_id": no_speech_token_id} if return_logprobs else {}
             parts = [self.generate(encoder_hidden[i:i + self.max_batch], max_length, force_eos_step, None, chunk,
                                    None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead,
-                                   return_timestamps, **(tt or {}), **lp)
+                                   return_timestamps, **(tt or {}), **lp, **samp(i, i + self.max_batch))
                      for i in range(0, encoder_hidden.shape[0], self.max_batch)]
             pad = self.config["pad_token_id"]
             cat = lambda ps, value: torch.cat([torch.nn.functional.pad(p, (0, max(q.shape[1] for q in ps) - p.shape[1]), value=value) for p in ps], dim=0)
@@ -559,7 +612,7 @@ class WhisperDecoderEngine:
                 return cat([p[0] for p in parts], pad), cat([p[1] for p in parts], 0.0)
             return cat(parts, pad)
         self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, **(tt or {}),
-                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id)
+                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id, **samp(0, None))
         if chunk <= 0:
             cur, _nu = self.run(lookahead)
         else:
@@ -573,6 +626,67 @@ class WhisperDecoderEngine:
             scores = self.read_logprobs(ids)
             return (ids, self.read_token_timestamps(cur), scores) if tt else (ids, scores)
         return (self.read_ids(cur), self.read_token_timestamps(cur)) if tt else self.read_ids(cur)
+
+    def generate_with_fallback(self, encoder_hidden, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), compression_ratio_threshold=2.4,
+                               logprob_threshold=-1.0, no_speech_threshold=0.6, no_speech_token_id=None, text_of=None, seed: int = 0,
+                               seeds=None, **generate_kwargs):
+        """openai-whisper's decode_with_fallback, batched: decode every row at temperatures[0]; a row needs another try when
+        compression_ratio(text) > compression_ratio_threshold or avg_logprob < logprob_threshold -- unless no_speech_prob >
+        no_speech_threshold (silence: the transcript is dropped anyway); a threshold of None is skipped (no_speech also without a
+        `no_speech_token_id`).  The encoder rows that need it are gathered and decoded again at the next temperature, until none is left
+        or the list ends; a row keeps the result of the last temperature it was decoded at.  Row i draws with `seed + i` at every
+        temperature (or with `seeds[i]`, for a caller whose rows are not consecutive utterances), whichever other rows are decoded beside
+        it.  `text_of(ids) -> str` gives the text whose compression ratio is taken
+        (default: the config's token decoder, or the ids in decimal).  Returns (ids int32 [B, len] padded with pad_token_id, DecodeScores,
+        temperature_used float32 [B])."""
+        import torch
+        from .text import compression_ratio
+        temperatures = [float(t) for t in temperatures]
+        if not temperatures:
+            raise ValueError("temperatures must not be empty")
+        for key in ("temperature", "return_logprobs", "num_beams", "return_scores", "return_token_timestamps"):
+            if key in generate_kwargs:
+                raise ValueError(f"generate_with_fallback does not take {key}")
+        text_of = text_of or _default_text_of(self.config)
+        eos, pad = self.config["eos_token_id"], self.config["pad_token_id"]
+        B = int(encoder_hidden.shape[0])
+        row_seed = [int(seed) + i for i in range(B)] if seeds is None else [int(x) for x in seeds]
+        if len(row_seed) < B:
+            raise ValueError(f"seeds needs one entry per utterance ({B}), got {len(row_seed)}")
+        todo = list(range(B))
+        rows = [None] * B                      # per original row: (ids, token_logprobs, sum_logprob, no_speech_prob, temperature)
+        for t in temperatures:
+            hidden = encoder_hidden if len(todo) == B else encoder_hidden[torch.as_tensor(todo, device=encoder_hidden.device)]
+            ids, sc = self.generate(hidden, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
+                                    seeds=[row_seed[i] for i in todo], **generate_kwargs)
+            avg = sc.avg_logprob.cpu().tolist()
+            nsp = sc.no_speech_prob.cpu().tolist() if sc.no_speech_prob is not None else [None] * len(todo)
+            host_ids = ids.cpu().tolist()
+            again = []
+            for k, i in enumerate(todo):
+                rows[i] = (ids[k], sc.token_logprobs[k], sc.sum_logprob[k], None if sc.no_speech_prob is None else sc.no_speech_prob[k], t)
+                row = host_ids[k]
+                if eos in row[1:]:
+                    row = row[:row.index(eos, 1) + 1]
+                needs = False
+                if compression_ratio_threshold is not None:
+                    text = text_of(row)
+                    needs = bool(text) and compression_ratio(text) > compression_ratio_threshold
+                if logprob_threshold is not None and avg[k] < logprob_threshold:
+                    needs = True
+                if no_speech_threshold is not None and nsp[k] is not None and nsp[k] > no_speech_threshold:
+                    needs = False
+                if needs:
+                    again.append(i)
+            todo = again
+            if not todo:
+                break
+        width = max(r[0].shape[0] for r in rows)
+        padded = lambda x, value: torch.nn.functional.pad(x, (0, width - x.shape[0]), value=value)
+        ids = torch.stack([padded(r[0], pad) for r in rows])
+        scores = DecodeScores(ids, torch.stack([padded(r[1], 0.0) for r in rows]), torch.stack([r[2] for r in rows]),
+                              torch.stack([r[3] for r in rows]) if rows[0][3] is not None else None, eos)
+        return ids, scores, torch.tensor([r[4] for r in rows], dtype=torch.float32, device=ids.device)
 
     def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1,
                return_token_timestamps: bool = False) -> "DecodeStream":
@@ -635,6 +749,7 @@ class DecodeStream:
         dec._set_timestamp_rules(False)     # a timestamp decode before on this handle left the mode on
         dec._set_beam_search(1)             # ... and so did a beam decode
         dec._set_token_timestamps(())       # ... and a decode with token-level timestamps
+        dec._set_sampling(0.0)              # ... and a sampled decode
         self.pool_rows = int(pool_rows) if pool_rows else 4 * self.slots
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_decoder_stream_begin(self._h, self.slots, self.pool_rows, ctypes.byref(self._p), ctypes.c_void_p(stream)),
@@ -802,7 +917,11 @@ class WhisperPipeline:
         def item(k: int, i: int):
             enc, dec = self.engines[k]
             with torch.cuda.stream(self.streams[k]):
-                return dec.generate(enc(mel_batches[i]), **(gen_kwargs[i] if gen_kwargs is not None else {}))
+                kw = dict(gen_kwargs[i]) if gen_kwargs is not None else {}
+                fallback = kw.pop("temperature_fallback", None)      # a dict of generate_with_fallback's own arguments
+                if fallback is not None:
+                    return dec.generate_with_fallback(enc(mel_batches[i]), **fallback, **kw)
+                return dec.generate(enc(mel_batches[i]), **kw)
 
         return run_workers(n, len(self.engines), item, setup=setup, teardown=lambda k: self.streams[k].synchronize())
 
