@@ -201,6 +201,18 @@ size_t wt_dbg_skinny_qkv_append_scratch_bytes(void);
 int wt_dbg_skinny_qkv_append(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* q, void* kcache,
                              void* vcache, const int32_t* self_len, int B, int d, int s_cap, int w_half, int kv_half, int w_nt, float scale,
                              void* scratch, void* stream);
+/* The q|k|v launch of the decode step with the residual half of the folded cross-attention query on board (LP_QKV, d <= 1024):
+ * wt_dbg_skinny_qkv_append's arguments and outputs, bit for bit, plus uh [B][d] = Wh . X + c over the RAW rows X in the same launch
+ * (Wh [d][d] float or half like W: columns [d, 2d) of the folded weight, contiguous; c [d]).
+ * scratch: wt_dbg_skinny_qkv_append_scratch_bytes() bytes. */
+int wt_dbg_skinny_qkv_hoist(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* q, void* kcache,
+                            void* vcache, const int32_t* self_len, const void* Wh, const float* c, float* uh, int B, int d, int s_cap,
+                            int w_half, int kv_half, int w_nt, float scale, void* scratch, void* stream);
+/* The pair launch that follows it (LP_PAIR): h1 = h + Wo . a + bo and u = Wa . a + uh (Wa [d][d]: columns [0, d) of the folded weight,
+ * contiguous; Wo / Wa float or half).  The context comes from a [B][d] or, with a NULL, from the two split partials part [B][d/64][2][68]
+ * of a self-attention with the merge deferred.  The pair launch has ONE load policy (non-temporal weight loads), hence no w_nt. */
+int wt_dbg_skinny_pair_hoisted(const float* a, const float* part, const void* Wo, const float* bo, const float* h, float* h1, const void* Wa,
+                               const float* uh, float* u, int B, int d, int w_half, void* stream);
 /* The plain greedy tail as the engine enqueues it: greedy_select_kernel over logits [B][V] (part_val / part_idx NULL), or, with logits NULL,
  * the fused form over precomputed partials part_val / part_idx [B][n_parts] (the vocabulary GEMV's); then greedy_finish_kernel<false>.
  * mask bytes [V] (device), forced a HOST array [max_length] (forced token of sequence index i, < 0: none), ids int32 [B][max_length] and

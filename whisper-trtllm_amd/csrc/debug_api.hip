@@ -499,6 +499,39 @@ extern "C" int wt_dbg_skinny_qkv_append(const float* X, const float* ln_w, const
     return rc_of(launch_skinny(k, s));
 }
 
+// ---- the q|k|v and pair launches with the residual half of the folded query hoisted (engine.hip: enqueue_layer_part, d <= 1024) ----
+extern "C" int wt_dbg_skinny_qkv_hoist(const float* X, const float* ln_w, const float* ln_b, const void* W, const float* bias, float* q, void* kcache,
+                                       void* vcache, const int32_t* self_len, const void* Wh, const float* c, float* uh, int B, int d, int s_cap,
+                                       int w_half, int kv_half, int w_nt, float scale, void* scratch, void* stream) {
+    if (!X || !ln_w || !ln_b || !W || !q || !kcache || !vcache || !self_len || !scratch || !Wh || !c || !uh) return -22;
+    if (B < 1 || B > MAX_ROWS || d < 64 || d > 1024 || (d & 63) || s_cap < 1) return -22;
+    for (int b = 0; b < B; ++b)
+        if (self_len[b] < 0 || self_len[b] >= s_cap) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    DecState h;
+    memset(&h, 0, sizeof h);
+    for (int b = 0; b < B; ++b) h.self_len[b] = self_len[b];
+    int rc = upload_state(scratch, h, s);
+    if (rc) return rc;
+    SkinnyParams k = qkv_append_skinny_params(X, ln_w, ln_b, W, bias, q, kcache, vcache, (const DecState*)scratch, B, d, s_cap, w_nt ? 1 : 0,
+                                              w_half ? 1 : 0, kv_half ? 1 : 0);
+    k.q_scale = scale;
+    const SkinnyParams k2 = qfold_resid_skinny_params(X, Wh, c, uh, (const DecState*)scratch, B, d, w_nt ? 1 : 0, w_half ? 1 : 0);
+    return rc_of(launch_skinny_qkv_hoist(k, k2, s));
+}
+extern "C" int wt_dbg_skinny_pair_hoisted(const float* a, const float* part, const void* Wo, const float* bo, const float* h, float* h1,
+                                          const void* Wa, const float* uh, float* u, int B, int d, int w_half, void* stream) {
+    if ((a != nullptr) == (part != nullptr) || !Wo || !bo || !h || !h1 || !Wa || !uh || !u) return -22;   // exactly one source of the context
+    if (B < 1 || B > MAX_ROWS || d < 64 || d > 1024 || (d & 63)) return -22;
+    SkinnyParams k;
+    memset(&k, 0, sizeof k);
+    k.X = a; k.xmode = XMODE_PLAIN; k.W = (const float*)Wo; k.bias = bo; k.resid = h; k.Y = h1; k.B = B; k.N = d; k.K = d; k.q_scale = 1.f;
+    k.w_nt = 1; k.w_half = w_half ? 1 : 0;   // (the pair launch streams its weights non-temporally whatever w_nt says)
+    if (part) { k.parts = part; k.parts_nsplit = 2; k.parts_H = d / HEAD_DIM; }
+    const SkinnyParams k2 = qfold_ctx_skinny_params(a, part, Wa, uh, u, nullptr, B, d, 1, w_half ? 1 : 0);
+    return rc_of(launch_skinny_pair(k, k2, (hipStream_t)stream));
+}
+
 // ---- decode attention as the step graph launches it: the length per row from a device DecState (fixed_len = 0), the skip-finished-rows
 // and slot_row forms, either load policy ----
 // a host DecState with self_len[b] = self_len[b] (b < B), refusing a length outside the cache

@@ -58,6 +58,8 @@ struct DecLayerW {
     const float *ckv_w, *ckv_b, *co_w, *co_b;
     const float *ln3_w, *ln3_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
     const void* ckv_w3 = nullptr;   // cross k|v weights as three bf16 planes (launch_gemm_x3)
+    // d <= 1024: columns [0, d) / [d, 2d) of fold_w as two contiguous [d][d] matrices in the engine's weight precision (build_fold_halves)
+    const void *fold_wa = nullptr, *fold_wh = nullptr;
 };
 
 struct EvTimer {
@@ -72,12 +74,14 @@ struct EvTimer {
 struct WeightStore {
     char* base = nullptr;
     char* x3 = nullptr;    // fp32 engines: the big GEMMs' weights once more as three bf16 planes each (launch_gemm_x3), shared like `base`
+    char* fold = nullptr;  // decoder engines, d <= 1024: the two halves of every layer's fold_w (build_fold_halves), shared like `base`
     int device = 0;
     ~WeightStore() {
-        if (!base && !x3) return;
+        if (!base && !x3 && !fold) return;
         DeviceGuard guard(device);
         if (base) hipFree(base);
         if (x3) hipFree(x3);
+        if (fold) hipFree(fold);
     }
 };
 
@@ -112,6 +116,7 @@ struct wt_engine {
     int kv_esz = 4;        // bytes per element of the RESIDENT caches (2 in fp16 engines; Session-path caches are the caller's f32)
     void* enc_h = nullptr; // fp16 engines: half copy of the encoder memory [B][S][d], the A operand of the cross-K/V projection
     float *dh = nullptr, *dh2 = nullptr, *dq = nullptr, *datt = nullptr, *dffn = nullptr, *part = nullptr, *logits = nullptr;
+    float* duh = nullptr;   // [B][d] residual half of the folded cross-attention query, q|k|v launch -> pair launch (enqueue_layer_part)
     int* att_cnt = nullptr;
     float* sel_val = nullptr;
     int* sel_idx = nullptr;
@@ -306,6 +311,36 @@ static int build_x3_weights(wt_engine* e) {
     return WT_OK;
 }
 
+// Decoder engines, d <= 1024: the folded cross-attention query u = fold_w . [a ; h] + fold_c is computed in two launches (enqueue_layer_part),
+// each over one column half of fold_w [d][2d].  A GEMV streams contiguous rows, so the halves are repacked ONCE per engine into two
+// [d][d] matrices per layer (a strided device-to-device copy; 2 d^2 weight elements per layer on top of the blob's: 8.4 MB at medium.en
+// fp32), shared by the handles wt_engine_clone makes.
+static int build_fold_halves(wt_engine* e) {
+    if (e->kind != WT_KIND_DECODER || e->d > 1024 || e->dec_layers.empty()) return WT_OK;
+    const size_t d = e->d, esz = e->w_half ? 2 : 4, half = align_up(d * d * esz, 256);
+    const size_t total = half * 2 * e->dec_layers.size();
+    hipError_t he = hipMalloc((void**)&e->weights->fold, total);
+    if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for the folded-query halves failed: %s", total, hipGetErrorString(he));
+    hipStream_t up = nullptr;
+    he = hipStreamCreateWithFlags(&up, hipStreamNonBlocking);
+    size_t off = 0;
+    for (DecLayerW& l : e->dec_layers) {
+        char *wa = e->weights->fold + off, *wh = wa + half;
+        const char* src = (const char*)l.fold_w;
+        if (he == hipSuccess) he = hipMemcpy2DAsync(wa, d * esz, src, 2 * d * esz, d * esz, d, hipMemcpyDeviceToDevice, up);
+        if (he == hipSuccess) he = hipMemcpy2DAsync(wh, d * esz, src + d * esz, 2 * d * esz, d * esz, d, hipMemcpyDeviceToDevice, up);
+        l.fold_wa = wa; l.fold_wh = wh;
+        off += 2 * half;
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(up);
+    if (up) hipStreamDestroy(up);
+    if (he != hipSuccess) {
+        for (DecLayerW& l : e->dec_layers) l.fold_wa = l.fold_wh = nullptr;
+        return fail(WT_E_HIP, "repacking the folded-query weights failed: %s", hipGetErrorString(he));
+    }
+    return WT_OK;
+}
+
 extern "C" int wt_engine_open(const void* blob, size_t nbytes, int device, wt_engine** out) {
     if (!blob || !out) return fail(WT_E_INVALID, "wt_engine_open: null argument");
     *out = nullptr;
@@ -433,7 +468,8 @@ extern "C" int wt_engine_open(const void* blob, size_t nbytes, int device, wt_en
     }
     {   // fp32 engines: the weights of the big GEMMs once more as three bf16 planes (wt_common.h: launch_gemm_x3)
         static const bool x3_on = !(tuning_env("WT_GEMM_X3") && atoi(tuning_env("WT_GEMM_X3")) == 0);   // A/B switch: native fp32 MFMA GEMMs
-        const int rc = (x3_on && e->precision == WT_F32 && (e->d % 16) == 0 && (e->F % 16) == 0) ? build_x3_weights(e) : WT_OK;
+        int rc = (x3_on && e->precision == WT_F32 && (e->d % 16) == 0 && (e->F % 16) == 0) ? build_x3_weights(e) : WT_OK;
+        if (rc == WT_OK) rc = build_fold_halves(e);
         if (rc) {
             std::string keep = g_err;
             wt_engine_close(e);
@@ -697,6 +733,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     const size_t o_ench = take(e->w_half ? (size_t)enc_rows * e->S * d * 2 : 0);
     const size_t o_enc3 = take(e->use_x3 ? (size_t)enc_rows * e->S * d * 6 : 0);
     const size_t o_h = take((size_t)B * d * 4), o_h2 = take((size_t)B * d * 4), o_q = take((size_t)B * d * 4), o_att = take((size_t)B * d * 4), o_f = take((size_t)B * e->F * 4);
+    const size_t o_uh = take((size_t)B * d * 4);
     const size_t o_cnt = take((size_t)B * e->H * 4);
     const size_t o_selv = take((size_t)B * SEL_PARTS_CAP * 4), o_seli = take((size_t)B * SEL_PARTS_CAP * 4);
     const size_t o_part = take((size_t)B * e->H * 16 * PART_STRIDE * 4), o_lg = take((size_t)B * e->V * 4);
@@ -716,6 +753,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     char* b = e->dec_ws;
     e->self_k = (float*)(b + o_sk); e->self_v = (float*)(b + o_sv); e->cross_k = (float*)(b + o_ck); e->cross_v = (float*)(b + o_cv);
     e->dh = (float*)(b + o_h); e->dh2 = (float*)(b + o_h2); e->dq = (float*)(b + o_q); e->datt = (float*)(b + o_att); e->att_cnt = (int*)(b + o_cnt); e->sel_val = (float*)(b + o_selv); e->sel_idx = (int*)(b + o_seli); e->dffn = (float*)(b + o_f); e->part = (float*)(b + o_part);
+    e->duh = (float*)(b + o_uh);
     e->logits = (float*)(b + o_lg); e->st = (DecState*)(b + o_st); e->ids = (int*)(b + o_ids); e->unfinished = (int*)(b + o_unf);
     e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows); e->ts_part = (TsPart*)(b + o_tsp);
     e->lp_part = (float4*)(b + o_lpp); e->lp_side = (float*)(b + o_lps); e->lp_tok = (float*)(b + o_lpt); e->lp_sum = (float*)(b + o_lpsum); e->lp_nsp = (float*)(b + o_lpn);
@@ -788,8 +826,13 @@ struct StepIO {
 enum { LP_QKV = 0, LP_SELF_ATTN, LP_PAIR, LP_CROSS_ATTN, LP_CROSS_OUT, LP_FC1, LP_FC2, LP_COUNT };
 static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, float* h1, int part, hipStream_t s) {
     static const bool defer = tuning_env("WT_NO_DEFER_MERGE") == nullptr;  // A/B switch
+    // A/B switch: WT_QFOLD_HOIST=0 keeps the whole folded query in the pair launch (K = 2d over [a ; h], x_direct / half-staged)
+    static const bool hoist_on = !(tuning_env("WT_QFOLD_HOIST") && atoi(tuning_env("WT_QFOLD_HOIST")) == 0);
     const int d = e->d, B = io.B, H = e->H;
     const DecLayerW& l = e->dec_layers[i];
+    // The half of the folded query that multiplies the layer input h does not depend on the self-attention: it rides in the q|k|v launch
+    // (whose workgroups leave compute units idle) and reaches the pair launch as a residual.  Where the repacked halves exist: d <= 1024.
+    const bool hoist = hoist_on && l.fold_wa && l.fold_wh && d <= 1024;
     const size_t self_layer = (size_t)i * B * H * io.self_cap * HEAD_DIM * io.kv_esz, cross_layer = (size_t)i * io.cross_rows * H * e->S * HEAD_DIM * io.kv_esz;
     float* sk = (float*)((char*)io.self_k + self_layer);
     float* sv = (float*)((char*)io.self_v + self_layer);
@@ -804,7 +847,12 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
     switch (part) {
     case LP_QKV:  // self attention (model.py:273-281, 283-304): LN -> q|k|v, append k/v row in place
         k = qkv_append_skinny_params(h, l.ln1_w, l.ln1_b, l.qkv_w, l.qkv_b, e->dq, sk, sv, e->st, B, d, io.self_cap, e->nt_loads, wh, kvh);
-        LAUNCH(launch_skinny(k, s));
+        if (hoist) {   // + uh = fold_wh . h + fold_c on the raw row, in the same launch
+            k2 = qfold_resid_skinny_params(h, l.fold_wh, l.fold_c, e->duh, e->st, B, d, e->nt_loads, wh);
+            LAUNCH(launch_skinny_qkv_hoist(k, k2, s));
+        } else {
+            LAUNCH(launch_skinny(k, s));
+        }
         break;
     case LP_SELF_ATTN:
         a.q = e->dq; a.kcache = sk; a.vcache = sv; a.part = e->part; a.cnt = e->att_cnt; a.out = e->datt; a.st = e->st; a.B = B; a.H = H; a.s_cap = io.self_cap;
@@ -819,11 +867,16 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
         // by the cross-attention kernel (model.py:261-272 semantics, one dependent launch fewer per layer)
         k.X = e->datt; k.xmode = XMODE_PLAIN; k.W = l.o_w; k.bias = l.o_b; k.resid = h;
         k.Y = h1; k.st = e->st; k.B = B; k.N = d; k.K = d; k.q_scale = 1.f; k.w_nt = e->nt_loads; k.w_half = wh;
-        k2.X = e->datt; k2.X2 = h; k2.xmode = XMODE_PLAIN; k2.x_direct = 1; k2.W = l.fold_w; k2.bias = l.fold_c;
-        k2.Y = e->dq; k2.st = e->st; k2.B = B; k2.N = d; k2.K = 2 * d; k2.q_scale = 1.f; k2.w_nt = e->nt_loads; k2.w_half = wh;
+        if (hoist) {   // u = fold_wa . a + uh: both halves of the launch read only `a`, staged (and merged) once per workgroup
+            k2 = qfold_ctx_skinny_params(e->datt, defer && io.nsplit_self == 2 ? e->part : nullptr, l.fold_wa, e->duh, e->dq, e->st, B, d,
+                                         e->nt_loads, wh);
+        } else {
+            k2.X = e->datt; k2.X2 = h; k2.xmode = XMODE_PLAIN; k2.x_direct = 1; k2.W = l.fold_w; k2.bias = l.fold_c;
+            k2.Y = e->dq; k2.st = e->st; k2.B = B; k2.N = d; k2.K = 2 * d; k2.q_scale = 1.f; k2.w_nt = e->nt_loads; k2.w_half = wh;
+        }
         if (defer && io.nsplit_self == 2) {   // the self-attention context `a` arrives as two split partials per (utterance, head)
             k.parts = e->part; k.parts_nsplit = 2; k.parts_H = H;
-            k2.parts = e->part; k2.parts_nsplit = 2; k2.parts_H = H;
+            if (!hoist) { k2.parts = e->part; k2.parts_nsplit = 2; k2.parts_H = H; }
         }
         LAUNCH(launch_skinny_pair(k, k2, s));
         break;
@@ -1889,7 +1942,7 @@ extern "C" int wt_decoder_time_cross_attention(wt_engine* e, int iters, float* a
 // step) are captured into a hipGraph and replayed `iters` times between two hipEvents recorded on the launch stream.  (Events
 // cannot bracket single kernels inside the step graph; an eager pass adds dispatch gaps.)  The residual stream is not advanced:
 // every launch reads the current buffers, which is what its duration depends on.  Only to be called BETWEEN steps of a decode:
-// the launches scribble on the step scratch (dq, datt, dh2, dffn, the attention partials and the self-cache row at self_len),
+// the launches scribble on the step scratch (dq, duh, datt, dh2, dffn, the attention partials and the self-cache row at self_len),
 // all of which the next step rewrites before reading.
 extern "C" int wt_decoder_time_kernel(wt_engine* e, const char* which, int iters, float* avg_us, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER || !which || !avg_us || iters < 1) return fail(WT_E_INVALID, "wt_decoder_time_kernel: bad arguments");

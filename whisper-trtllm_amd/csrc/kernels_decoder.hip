@@ -576,6 +576,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_pair_kernel(c
     else skinny_body<NB, V, NW, true, HALF_B, false, WH>(b, pb.nsplit, pb.KS, pb.rows_per_group, blockIdx.x - pa.grid);
 }
 
+// The q|k|v launch with a passenger ("Hoisted residual half"): blocks [0, pa.grid) run `a` -- LayerNorm -> q|k|v -> append,
+// the very instantiation and plan skinny_gemm_kernel runs it with, so q and the cache rows keep their bits -- and the rest run the plain
+// GEMV `b` over the raw residual row (uh = fold_wh . h + fold_c) on compute units the q|k|v range leaves idle.  Block-uniform branch.
+template <int NB, int V, int NW, bool W_NT, bool WH = false>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_hoist_kernel(const SkinnyParams a, const SkinnyPlan pa,
+                                                                              const SkinnyParams b, const SkinnyPlan pb) {
+    if ((int)blockIdx.x < pa.grid) skinny_body<NB, V, NW, W_NT, false, false, WH>(a, pa.nsplit, pa.KS, pa.rows_per_group, blockIdx.x);
+    else skinny_body<NB, V, NW, W_NT, false, false, WH>(b, pb.nsplit, pb.KS, pb.rows_per_group, blockIdx.x - pa.grid);
+}
+
 template <int NB, int V, int NW>
 static hipError_t skinny_plan(const SkinnyParams& p, SkinnyPlan* out, int tg_override = 0) {
     if (p.B < 1 || p.B > NB || (p.K & 3)) return hipErrorInvalidValue;
@@ -622,7 +632,11 @@ static hipError_t skinny_smem_attr() {
                               reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, true, true, true>),
                               reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, false, true, true>),
                               reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, false, true>),
-                              reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, true, true>)}) {
+                              reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, true, true>),
+                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, false>),
+                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, true>),
+                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, false, true>),
+                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, true, true>)}) {
             hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
             if (e != hipSuccess) return e;
         }
@@ -760,6 +774,35 @@ static hipError_t skinny_pair_cfg(const SkinnyParams& a, const SkinnyParams& b, 
     return hipGetLastError();
 }
 
+template <int NB, int V, int NW>
+static hipError_t skinny_hoist_cfg(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s) {
+    SkinnyPlan pa, pb;
+    hipError_t e = skinny_plan<NB, V, NW>(a, &pa);   // the q|k|v range: the plan launch_skinny gives it alone
+    if (e == hipSuccess) e = skinny_plan<NB, V, NW>(b, &pb);
+    // The passenger takes the workgroups the q|k|v range leaves free in its last round over the 256 compute units: fewer, fatter row
+    // groups until it fits (medium.en batch 8: 192 + 64 workgroups, every wave of either range streams four rows).  Row groups at most
+    // four times the usual size; where even those do not fit (or the q|k|v range fills its rounds exactly: no such shape today) the
+    // passenger keeps its usual plan and spills into another round.
+    const int room = (pa.grid + 255) / 256 * 256;
+    if (e == hipSuccess && pa.grid + pb.grid > room && room > pa.grid) {
+        SkinnyPlan fat = pb;
+        for (int tg = NB == 8 ? 512 : 1024; e == hipSuccess && pa.grid + fat.grid > room && tg >= 256; tg >>= 1) e = skinny_plan<NB, V, NW>(b, &fat, tg);
+        if (e == hipSuccess && pa.grid + fat.grid <= room) pb = fat;
+    }
+    if (e == hipSuccess) e = skinny_smem_attr<NB, V, NW>();
+    if (e != hipSuccess) return e;
+    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
+    const dim3 grid(pa.grid + pb.grid), blk(64 * NW);
+    if (a.w_half) {
+        if (a.w_nt) hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, true, true>), grid, blk, smem, s, a, pa, b, pb);
+        else hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, false, true>), grid, blk, smem, s, a, pa, b, pb);
+    } else {
+        if (a.w_nt) hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, true>), grid, blk, smem, s, a, pa, b, pb);
+        else hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, false>), grid, blk, smem, s, a, pa, b, pb);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_skinny_gelu_in_probe(const SkinnyParams& p, hipStream_t s) {
     if (p.B < 1 || p.B > 8 || p.K <= 1024 || p.xmode != XMODE_PLAIN || !p.ln_w || !p.ln_b || !p.bias) return hipErrorInvalidValue;
     SkinnyPlan pl;
@@ -806,6 +849,18 @@ hipError_t launch_skinny_pair(const SkinnyParams& a, const SkinnyParams& b, hipS
     if (a.B <= 4) return skinny_pair_cfg<4, 4, 4>(a, b, s);
     if (a.B <= 8) return skinny_pair_cfg<8, 4, 4>(a, b, s);
     return skinny_pair_cfg<16, 2, 8>(a, b, s);
+}
+
+hipError_t launch_skinny_qkv_hoist(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s) {
+    if (a.B != b.B || a.B < 1 || a.B > 16 || (a.K & 3) || (b.K & 3)) return hipErrorInvalidValue;
+    if (a.ymode != YMODE_QKV_APPEND || a.xmode != XMODE_LAYERNORM || a.parts || a.X2 || a.x_direct) return hipErrorInvalidValue;
+    // the passenger: a plain GEMV over whole LDS-staged rows
+    if (b.ymode != YMODE_PLAIN || b.xmode != XMODE_PLAIN || b.parts || b.X2 || b.x_direct || b.K > 1024 || !b.X || !b.W || !b.Y) return hipErrorInvalidValue;
+    if (a.w_half != b.w_half || (a.w_nt != 0) != (b.w_nt != 0)) return hipErrorInvalidValue;
+    if (a.B <= 2) return skinny_hoist_cfg<2, 4, 4>(a, b, s);
+    if (a.B <= 4) return skinny_hoist_cfg<4, 4, 4>(a, b, s);
+    if (a.B <= 8) return skinny_hoist_cfg<8, 4, 4>(a, b, s);
+    return skinny_hoist_cfg<16, 2, 8>(a, b, s);
 }
 
 // ------------------------------------------------------------------------------------------------ decode attention

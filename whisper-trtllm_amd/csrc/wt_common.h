@@ -278,6 +278,9 @@ hipError_t launch_skinny_gelu_in_probe(const SkinnyParams& p, hipStream_t s);   
 int skinny_grid(const SkinnyParams& p);  // workgroups launch_skinny uses for p (column count of am_val / am_idx), -1 if p is invalid
 // two independent skinny GEMMs (same batch) in ONE launch: blocks [0, grid_a) run `a`, the rest run `b`
 hipError_t launch_skinny_pair(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s);
+// the q|k|v launch (`a`: LayerNorm -> q|k|v -> append, exactly as launch_skinny runs it) carrying a plain LDS-staged GEMV `b` (K <= 1024)
+// on the workgroups it leaves idle: the residual half of the folded cross-attention query (qfold_resid_skinny_params)
+hipError_t launch_skinny_qkv_hoist(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s);
 hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s);
 
 constexpr int SELECT_CHUNKS = 8;   // vocabulary chunks (workgroups per row) of greedy_select_kernel / ts_select_kernel
@@ -458,6 +461,27 @@ inline SkinnyParams qkv_append_skinny_params(const float* h, const float* ln_w, 
     k.X = h; k.ln_w = ln_w; k.ln_b = ln_b; k.xmode = XMODE_LAYERNORM; k.W = (const float*)W; k.bias = bias;
     k.Y = q; k.kcache = (float*)kcache; k.vcache = (float*)vcache; k.st = st; k.B = B; k.N = 3 * d; k.K = d; k.ymode = YMODE_QKV_APPEND;
     k.d_model = d; k.s_cap = s_cap; k.q_scale = 0.125f; k.w_nt = w_nt; k.w_half = w_half; k.kv_half = kv_half;
+    return k;
+}
+// The folded cross-attention query u = fold_w . [a ; h] + fold_c in two launches (d <= 1024): the half that multiplies the layer input h
+// rides in the q|k|v launch (uh = fold_wh . h + fold_c, h raw), the half that multiplies the self-attention context `a` stays in the pair
+// launch with uh as its residual (u = fold_wa . a + uh).  fold_wa / fold_wh: columns [0, d) / [d, 2d) of fold_w as contiguous [d][d].
+inline SkinnyParams qfold_resid_skinny_params(const float* h, const void* fold_wh, const float* fold_c, float* uh, const DecState* st, int B,
+                                              int d, int w_nt, int w_half) {
+    SkinnyParams k;
+    memset(&k, 0, sizeof k);
+    k.X = h; k.xmode = XMODE_PLAIN; k.W = (const float*)fold_wh; k.bias = fold_c; k.Y = uh; k.st = st; k.B = B; k.N = d; k.K = d;
+    k.q_scale = 1.f; k.w_nt = w_nt; k.w_half = w_half;
+    return k;
+}
+// `a`: the context rows [B][d], or, with `parts`, the two split partials of the self-attention (SkinnyParams.parts, H = d / 64)
+inline SkinnyParams qfold_ctx_skinny_params(const float* a, const float* parts, const void* fold_wa, const float* uh, float* u,
+                                            const DecState* st, int B, int d, int w_nt, int w_half) {
+    SkinnyParams k;
+    memset(&k, 0, sizeof k);
+    k.X = a; k.xmode = XMODE_PLAIN; k.W = (const float*)fold_wa; k.resid = uh; k.Y = u; k.st = st; k.B = B; k.N = d; k.K = d;
+    k.q_scale = 1.f; k.w_nt = w_nt; k.w_half = w_half;
+    if (parts) { k.parts = parts; k.parts_nsplit = 2; k.parts_H = d / HEAD_DIM; }
     return k;
 }
 // final LayerNorm + vocabulary projection (no bias): plain logits [B][V] ...
