@@ -131,6 +131,40 @@ def test_every_batch_width_is_row_independent(wt, B):
         np.testing.assert_array_equal(ids[b], singles[b])
 
 
+def test_logprob_and_sampling_forms_at_batch_9(wt):
+    """Half weights at batch 9, the smallest batch of the 16-row shapes (more than 48 KiB of dynamic LDS per workgroup): the vocabulary GEMV
+    in its log-probability forms (one pair; two pairs with no_speech_token_id) and its sampling form (four waves).  The log-probability forms
+    score the ids the plain form picks -- the running argmax is the same code over the same scores -- and each row's log-probabilities are
+    those of the row decoded alone within 4 x LOGITS_TOL: either decode is within LOGITS_TOL of the fp16 oracle on every logit, and
+    x_tok - lse moves by at most |dx_tok| + max |dx|.  Sampling: finite log-probabilities <= 0 through each row's EOS, bitwise repeatable."""
+    cfg = wt.synthetic.get_config("toy-short")
+    weights = wt.synthetic.make_weights(cfg, 55)
+    enc = wt.WhisperEncoderEngine(wt.convert.build_encoder_engine(cfg, weights))
+    dec = wt.WhisperDecoderEngine(wt.convert.build_decoder_engine(cfg, weights, precision="float16"), cfg)
+    hidden = enc(torch.from_numpy(wt.synthetic.make_mel(cfg, index=500, batch=9)).cuda())
+    greedy = dec.generate(hidden)
+    for ns in (None, 5):
+        ids, sc = dec.generate(hidden, return_logprobs=True, no_speech_token_id=ns)
+        assert torch.equal(ids, greedy)
+        assert torch.isfinite(sc.token_logprobs).all() and (sc.token_logprobs <= 0).all()
+        for b in (0, 8):
+            alone, s1 = dec.generate(hidden[b:b + 1], return_logprobs=True, no_speech_token_id=ns)
+            n = alone.shape[1]
+            assert torch.equal(ids[b, :n], alone[0])
+            err = (sc.token_logprobs[b, :n] - s1.token_logprobs[0]).abs().max().item()
+            assert err <= 4 * LOGITS_TOL, (ns, b, err)
+            if ns is not None:
+                p, p1 = sc.no_speech_prob[b].item(), s1.no_speech_prob[0].item()
+                assert 0.0 < p < 1.0 and abs(p - p1) <= np.expm1(4 * LOGITS_TOL) * p1, (b, p, p1)
+    seeds = list(range(70, 79))
+    runs = [dec.generate(hidden, return_logprobs=True, temperature=0.8, seeds=seeds) for _ in range(2)]
+    (ids, sc), (ids2, sc2) = runs
+    assert torch.equal(ids, ids2) and torch.equal(sc.token_logprobs.view(torch.int32), sc2.token_logprobs.view(torch.int32))
+    assert torch.isfinite(sc.token_logprobs).all() and (sc.token_logprobs <= 0).all()
+    assert ((ids >= 0) & (ids < cfg["vocab_size"])).all()
+    assert torch.equal(dec.generate(hidden), greedy)   # and the plain form again, on the same handle
+
+
 def test_bitwise_reproducible_and_long_decode(wt):
     """tiny.en-shaped model, all 447 steps twice: bitwise equal ids and logits (no atomics on data), self-cache rows up to 447 in fp16."""
     cfg = wt.synthetic.get_config("whisper-tiny.en")

@@ -586,8 +586,42 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void skinny_hoist_kernel(
     else skinny_body<NB, V, NW, W_NT, false, false, WH>(b, pb.nsplit, pb.KS, pb.rows_per_group, blockIdx.x - pa.grid);
 }
 
-template <int NB, int V, int NW>
+// ---- launchers.  Every compile-time form of the kernels above is derived here once: the shape from the batch (skinny_for_batch), the
+// boolean forms from the run-time flags (with_flags), the dynamic-LDS size from the shape, and the launch itself in skinny_launch.
+// A shape: NB batch rows, V float4 activation chunks per lane and K-slice, NW waves per workgroup.
+template <int NB_, int V_, int NW_>
+struct SkinnyShape {
+    static constexpr int NB = NB_, V = V_, NW = NW_;
+    static constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);   // dynamic LDS: xs[NB][1024] + comb[2][NW][2 * NB]
+};
+
+// The shape ladder: f(shape of batch B).  16 rows: half-width K-slices, 8 waves per block.
+// SAMP (the shapes of the sampling forms): the 16-row sampling form runs FOUR waves per workgroup, not eight: one wave per SIMD has 512
+// registers per lane, and with two (256 each, of which the log-probability variant already takes 254-256) the Philox rounds spilled
+// 48-124 bytes per lane to scratch.  So every sampling shape is four waves wide, and <16, 2, 8> has no sampling form.
+template <bool SAMP, class F>
+static hipError_t skinny_for_batch(const int B, F&& f) {
+    if (B <= 2) return f(SkinnyShape<2, 4, 4>{});
+    if (B <= 4) return f(SkinnyShape<4, 4, 4>{});
+    if (B <= 8) return f(SkinnyShape<8, 4, 4>{});
+    if constexpr (SAMP) return f(SkinnyShape<16, 2, 4>{});
+    else return f(SkinnyShape<16, 2, 8>{});
+}
+static bool skinny_sampling(const SkinnyParams& p) { return p.ymode == YMODE_ARGMAX && p.am_samp; }
+
+// Run-time flags -> template arguments: with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...), and f
+// names the one instantiation its arguments select.  Only f's body decides which forms exist.
+template <class F>
+static hipError_t with_flags(F&& f) { return f(); }
+template <class F, class... Bs>
+static hipError_t with_flags(F&& f, const bool b, const Bs... bs) {
+    return b ? with_flags([&](auto... c) { return f(std::true_type{}, c...); }, bs...)
+             : with_flags([&](auto... c) { return f(std::false_type{}, c...); }, bs...);
+}
+
+template <class S>
 static hipError_t skinny_plan(const SkinnyParams& p, SkinnyPlan* out, int tg_override = 0) {
+    constexpr int NB = S::NB, V = S::V, NW = S::NW;
     if (p.B < 1 || p.B > NB || (p.K & 3)) return hipErrorInvalidValue;
     int nsplit = (p.parts && p.X2) ? 2 : 1;   // half-staged: a wave's K-slice must not straddle the [a ; X2] seam
     while (p.K / nsplit > 256 * V || (p.K % nsplit)) {
@@ -615,170 +649,75 @@ static hipError_t skinny_plan(const SkinnyParams& p, SkinnyPlan* out, int tg_ove
     out->nsplit = nsplit; out->KS = KS; out->rows_per_group = rows_per_group; out->grid = (groups + G - 1) / G;
     return hipSuccess;
 }
-
-template <int NB, int V, int NW>
-static hipError_t skinny_smem_attr() {
-    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
-    static PerDeviceFlag attr_set;
-    if (!attr_set.get() && smem > 48 * 1024) {
-        for (const void* f : {reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, true>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, false>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, true, true>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, false, true>),
-                              reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, false>),
-                              reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, true>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, true, false, true>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, false, false, true>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, true, true, true>),
-                              reinterpret_cast<const void*>(skinny_gemm_kernel<NB, V, NW, false, true, true>),
-                              reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, false, true>),
-                              reinterpret_cast<const void*>(skinny_pair_kernel<NB, V, NW, true, true>),
-                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, false>),
-                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, true>),
-                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, false, true>),
-                              reinterpret_cast<const void*>(skinny_hoist_kernel<NB, V, NW, true, true>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return e;
-        }
-        attr_set.set();
-    }
-    return hipSuccess;
+// both halves of a two-GEMV launch, planned alike
+template <class S>
+static hipError_t skinny_plan2(const SkinnyParams& a, const SkinnyParams& b, SkinnyPlan* pa, SkinnyPlan* pb, int tg_override = 0) {
+    const hipError_t e = skinny_plan<S>(a, pa, tg_override);
+    return e == hipSuccess ? skinny_plan<S>(b, pb, tg_override) : e;
 }
 
-template <int NB, int V, int NW>
-static hipError_t skinny_logprob_launch(const SkinnyParams& p, const SkinnyPlan& pl, hipStream_t s) {
-    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
-    static_assert(6 * NW * 2 * NB <= NB * 1024, "candidates + four pair arrays fit the activation staging area");
-    static PerDeviceFlag attr_set;
-    if (!attr_set.get() && smem > 48 * 1024) {
-        for (const void* f : {reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, false, 1>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, true, 1>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, false, 1>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, true, 1>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, false, 2>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, false, true, 2>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, false, 2>),
-                              reinterpret_cast<const void*>(skinny_logprob_kernel<NB, V, NW, true, true, 2>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+// The one place a skinny kernel is launched.  A shape that needs more than the default 48 KiB of dynamic LDS (16 rows) first has the
+// limit of the very kernel about to run raised: once per device and kernel -- and harmlessly again by a thread that races the first, or
+// under the thread-local stream capture of a step graph (the attribute is a property of the function, not a stream operation).
+template <auto KERNEL, class S, class... Args>
+static hipError_t skinny_launch(const int grid, hipStream_t s, const Args&... args) {
+    if constexpr (S::smem > 48 * 1024) {
+        static PerDeviceFlag attr_set;
+        if (!attr_set.get()) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, S::smem);
             if (e != hipSuccess) return e;
+            attr_set.set();
         }
-        attr_set.set();
     }
-#define WT_SK_LP(NT_, WH_, LP_) \
-    hipLaunchKernelGGL((skinny_logprob_kernel<NB, V, NW, NT_, WH_, LP_>), dim3(pl.grid), dim3(64 * NW), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group)
-    switch ((p.am_lp == 2 ? 4 : 0) | (p.w_nt ? 2 : 0) | (p.w_half ? 1 : 0)) {
-    case 0: WT_SK_LP(false, false, 1); break;
-    case 1: WT_SK_LP(false, true, 1); break;
-    case 2: WT_SK_LP(true, false, 1); break;
-    case 3: WT_SK_LP(true, true, 1); break;
-    case 4: WT_SK_LP(false, false, 2); break;
-    case 5: WT_SK_LP(false, true, 2); break;
-    case 6: WT_SK_LP(true, false, 2); break;
-    default: WT_SK_LP(true, true, 2); break;
-    }
-#undef WT_SK_LP
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(64 * S::NW), S::smem, s, args...);
     return hipGetLastError();
 }
 
-template <int NB, int V, int NW>
-static hipError_t skinny_sample_launch(const SkinnyParams& p, const SkinnyPlan& pl, hipStream_t s) {
-    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
-    static_assert(7 * NW * 2 * NB <= NB * 1024, "candidates + four pair arrays + scores fit the activation staging area");
-    if (!p.am_lp || !p.am_seeds || !p.am_sc || !(p.am_temp > 0.f)) return hipErrorInvalidValue;
-    static PerDeviceFlag attr_set;
-    if (!attr_set.get() && smem > 48 * 1024) {
-        for (const void* f : {reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, false, 1>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, true, 1>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, false, 1>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, true, 1>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, false, 2>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, false, true, 2>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, false, 2>),
-                              reinterpret_cast<const void*>(skinny_sample_kernel<NB, V, NW, true, true, 2>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return e;
-        }
-        attr_set.set();
-    }
-#define WT_SK_SM(NT_, WH_, LP_) \
-    hipLaunchKernelGGL((skinny_sample_kernel<NB, V, NW, NT_, WH_, LP_>), dim3(pl.grid), dim3(64 * NW), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group)
-    switch ((p.am_lp == 2 ? 4 : 0) | (p.w_nt ? 2 : 0) | (p.w_half ? 1 : 0)) {
-    case 0: WT_SK_SM(false, false, 1); break;
-    case 1: WT_SK_SM(false, true, 1); break;
-    case 2: WT_SK_SM(true, false, 1); break;
-    case 3: WT_SK_SM(true, true, 1); break;
-    case 4: WT_SK_SM(false, false, 2); break;
-    case 5: WT_SK_SM(false, true, 2); break;
-    case 6: WT_SK_SM(true, false, 2); break;
-    default: WT_SK_SM(true, true, 2); break;
-    }
-#undef WT_SK_SM
-    return hipGetLastError();
-}
-
-template <int NB, int V, int NW>
-static hipError_t skinny_launch_cfg(const SkinnyParams& p, hipStream_t s) {
+template <class S, bool SAMP>
+static hipError_t skinny_single(const SkinnyParams& p, hipStream_t s) {
+    constexpr int NB = S::NB, V = S::V, NW = S::NW;
     SkinnyPlan pl;
-    hipError_t e = skinny_plan<NB, V, NW>(p, &pl);
-    if (e == hipSuccess) e = skinny_smem_attr<NB, V, NW>();
+    const hipError_t e = skinny_plan<S>(p, &pl);
     if (e != hipSuccess) return e;
-    if (p.ymode == YMODE_ARGMAX && p.am_samp) {
-        if constexpr (NB <= 8) return skinny_sample_launch<NB, V, NW>(p, pl, s);
-        else return hipErrorInvalidValue;   // 16 rows: launch_skinny takes the four-wave form (skinny_sample_wide)
+    if constexpr (SAMP) {
+        static_assert(7 * NW * 2 * NB <= NB * 1024, "candidates + four pair arrays + scores fit the activation staging area");
+        if (!p.am_lp || !p.am_seeds || !p.am_sc || !(p.am_temp > 0.f)) return hipErrorInvalidValue;
+        return with_flags([&](auto NT, auto WH, auto LP2) {
+            return skinny_launch<skinny_sample_kernel<NB, V, NW, NT, WH, LP2 ? 2 : 1>, S>(pl.grid, s, p, pl.nsplit, pl.KS, pl.rows_per_group);
+        }, p.w_nt, p.w_half, p.am_lp == 2);
+    } else if (p.ymode == YMODE_ARGMAX && p.am_lp) {
+        static_assert(6 * NW * 2 * NB <= NB * 1024, "candidates + four pair arrays fit the activation staging area");
+        return with_flags([&](auto NT, auto WH, auto LP2) {
+            return skinny_launch<skinny_logprob_kernel<NB, V, NW, NT, WH, LP2 ? 2 : 1>, S>(pl.grid, s, p, pl.nsplit, pl.KS, pl.rows_per_group);
+        }, p.w_nt, p.w_half, p.am_lp == 2);
+    } else {
+        return with_flags([&](auto NT, auto AM, auto WH) {
+            return skinny_launch<skinny_gemm_kernel<NB, V, NW, NT, AM, WH>, S>(pl.grid, s, p, pl.nsplit, pl.KS, pl.rows_per_group);
+        }, p.w_nt, p.ymode == YMODE_ARGMAX, p.w_half);
     }
-    if (p.ymode == YMODE_ARGMAX && p.am_lp) return skinny_logprob_launch<NB, V, NW>(p, pl, s);
-    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
-#define WT_SK_LAUNCH(NT_, AM_, WH_) \
-    hipLaunchKernelGGL((skinny_gemm_kernel<NB, V, NW, NT_, AM_, WH_>), dim3(pl.grid), dim3(64 * NW), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group)
-    const int sel = (p.ymode == YMODE_ARGMAX ? 4 : 0) | (p.w_nt ? 2 : 0) | (p.w_half ? 1 : 0);
-    switch (sel) {
-    case 0: WT_SK_LAUNCH(false, false, false); break;
-    case 1: WT_SK_LAUNCH(false, false, true); break;
-    case 2: WT_SK_LAUNCH(true, false, false); break;
-    case 3: WT_SK_LAUNCH(true, false, true); break;
-    case 4: WT_SK_LAUNCH(false, true, false); break;
-    case 5: WT_SK_LAUNCH(false, true, true); break;
-    case 6: WT_SK_LAUNCH(true, true, false); break;
-    default: WT_SK_LAUNCH(true, true, true); break;
-    }
-#undef WT_SK_LAUNCH
-    return hipGetLastError();
 }
 
-template <int NB, int V, int NW>
+template <class S>
 static hipError_t skinny_pair_cfg(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s) {
     SkinnyPlan pa, pb;
-    hipError_t e = skinny_plan<NB, V, NW>(a, &pa);
-    if (e == hipSuccess) e = skinny_plan<NB, V, NW>(b, &pb);
+    hipError_t e = skinny_plan2<S>(a, b, &pa, &pb);
     // 8-wave workgroups (batch 9..16) are resident one per CU: a pair of more than 256 of them runs in two rounds, the second
     // half empty (measured 12.5 us per launch at medium.en batch 16 with 128 + 256 workgroups).  Re-plan both halves with fewer,
     // fatter row groups until the pair fits one round.
-    if (NW == 8)
-        for (int tg = 1024; e == hipSuccess && pa.grid + pb.grid > 256 && tg >= 256; tg >>= 1) {
-            e = skinny_plan<NB, V, NW>(a, &pa, tg);
-            if (e == hipSuccess) e = skinny_plan<NB, V, NW>(b, &pb, tg);
-        }
-    if (e == hipSuccess) e = skinny_smem_attr<NB, V, NW>();
+    if (S::NW == 8)
+        for (int tg = 1024; e == hipSuccess && pa.grid + pb.grid > 256 && tg >= 256; tg >>= 1) e = skinny_plan2<S>(a, b, &pa, &pb, tg);
     if (e != hipSuccess) return e;
-    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
     if (a.parts && a.X2) return hipErrorInvalidValue;   // the half-staged form exists for the second GEMV of a pair only
     if (a.w_half != b.w_half) return hipErrorInvalidValue;
-    const dim3 grid(pa.grid + pb.grid), blk(64 * NW);
-    if (a.w_half) {
-        if (b.parts && b.X2) hipLaunchKernelGGL((skinny_pair_kernel<NB, V, NW, true, true>), grid, blk, smem, s, a, pa, b, pb);
-        else hipLaunchKernelGGL((skinny_pair_kernel<NB, V, NW, false, true>), grid, blk, smem, s, a, pa, b, pb);
-    } else {
-        if (b.parts && b.X2) hipLaunchKernelGGL((skinny_pair_kernel<NB, V, NW, true>), grid, blk, smem, s, a, pa, b, pb);
-        else hipLaunchKernelGGL((skinny_pair_kernel<NB, V, NW, false>), grid, blk, smem, s, a, pa, b, pb);
-    }
-    return hipGetLastError();
+    return with_flags([&](auto HALF_B, auto WH) {
+        return skinny_launch<skinny_pair_kernel<S::NB, S::V, S::NW, HALF_B, WH>, S>(pa.grid + pb.grid, s, a, pa, b, pb);
+    }, b.parts && b.X2, a.w_half);
 }
 
-template <int NB, int V, int NW>
+template <class S>
 static hipError_t skinny_hoist_cfg(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s) {
     SkinnyPlan pa, pb;
-    hipError_t e = skinny_plan<NB, V, NW>(a, &pa);   // the q|k|v range: the plan launch_skinny gives it alone
-    if (e == hipSuccess) e = skinny_plan<NB, V, NW>(b, &pb);
+    hipError_t e = skinny_plan2<S>(a, b, &pa, &pb);   // the q|k|v range: the plan launch_skinny gives it alone
     // The passenger takes the workgroups the q|k|v range leaves free in its last round over the 256 compute units: fewer, fatter row
     // groups until it fits (medium.en batch 8: 192 + 64 workgroups, every wave of either range streams four rows).  Row groups at most
     // four times the usual size; where even those do not fit (or the q|k|v range fills its rounds exactly: no such shape today) the
@@ -786,42 +725,28 @@ static hipError_t skinny_hoist_cfg(const SkinnyParams& a, const SkinnyParams& b,
     const int room = (pa.grid + 255) / 256 * 256;
     if (e == hipSuccess && pa.grid + pb.grid > room && room > pa.grid) {
         SkinnyPlan fat = pb;
-        for (int tg = NB == 8 ? 512 : 1024; e == hipSuccess && pa.grid + fat.grid > room && tg >= 256; tg >>= 1) e = skinny_plan<NB, V, NW>(b, &fat, tg);
+        for (int tg = S::NB == 8 ? 512 : 1024; e == hipSuccess && pa.grid + fat.grid > room && tg >= 256; tg >>= 1) e = skinny_plan<S>(b, &fat, tg);
         if (e == hipSuccess && pa.grid + fat.grid <= room) pb = fat;
     }
-    if (e == hipSuccess) e = skinny_smem_attr<NB, V, NW>();
     if (e != hipSuccess) return e;
-    constexpr int smem = (NB * 1024 + 2 * NW * 2 * NB) * (int)sizeof(float);
-    const dim3 grid(pa.grid + pb.grid), blk(64 * NW);
-    if (a.w_half) {
-        if (a.w_nt) hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, true, true>), grid, blk, smem, s, a, pa, b, pb);
-        else hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, false, true>), grid, blk, smem, s, a, pa, b, pb);
-    } else {
-        if (a.w_nt) hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, true>), grid, blk, smem, s, a, pa, b, pb);
-        else hipLaunchKernelGGL((skinny_hoist_kernel<NB, V, NW, false>), grid, blk, smem, s, a, pa, b, pb);
-    }
-    return hipGetLastError();
+    return with_flags([&](auto NT, auto WH) {
+        return skinny_launch<skinny_hoist_kernel<S::NB, S::V, S::NW, NT, WH>, S>(pa.grid + pb.grid, s, a, pa, b, pb);
+    }, a.w_nt, a.w_half);
 }
 
 hipError_t launch_skinny_gelu_in_probe(const SkinnyParams& p, hipStream_t s) {
     if (p.B < 1 || p.B > 8 || p.K <= 1024 || p.xmode != XMODE_PLAIN || !p.ln_w || !p.ln_b || !p.bias) return hipErrorInvalidValue;
+    using S = SkinnyShape<8, 4, 4>;   // the probe's one form, whatever the batch
     SkinnyPlan pl;
-    hipError_t e = skinny_plan<8, 4, 4>(p, &pl);
+    const hipError_t e = skinny_plan<S>(p, &pl);
     if (e != hipSuccess) return e;
-    constexpr int smem = (8 * 1024 + 2 * 4 * 2 * 8) * (int)sizeof(float);
-    hipLaunchKernelGGL(skinny_gelu_in_probe_kernel, dim3(pl.grid), dim3(256), smem, s, p, pl.nsplit, pl.KS, pl.rows_per_group);
-    return hipGetLastError();
+    return skinny_launch<skinny_gelu_in_probe_kernel, S>(pl.grid, s, p, pl.nsplit, pl.KS, pl.rows_per_group);
 }
-
-// The 16-row sampling form runs FOUR waves per workgroup, not eight: one wave per SIMD has 512 registers per lane, and with two (256
-// each, of which the log-probability variant already takes 254-256) the Philox rounds spilled 48-124 bytes per lane to scratch.
-static bool skinny_sample_wide(const SkinnyParams& p) { return p.B > 8 && p.ymode == YMODE_ARGMAX && p.am_samp; }
 
 int skinny_grid(const SkinnyParams& p) {  // workgroups launch_skinny will use for p (the column count of am_val / am_idx)
     SkinnyPlan pl;
-    if (skinny_sample_wide(p)) return skinny_plan<16, 2, 4>(p, &pl) == hipSuccess ? pl.grid : -1;
-    hipError_t e = p.B <= 2 ? skinny_plan<2, 4, 4>(p, &pl) : p.B <= 4 ? skinny_plan<4, 4, 4>(p, &pl) : p.B <= 8 ? skinny_plan<8, 4, 4>(p, &pl)
-                                                                                                   : skinny_plan<16, 2, 8>(p, &pl);
+    const auto plan = [&](auto sh) { return skinny_plan<decltype(sh)>(p, &pl); };
+    const hipError_t e = skinny_sampling(p) ? skinny_for_batch<true>(p.B, plan) : skinny_for_batch<false>(p.B, plan);
     return e == hipSuccess ? pl.grid : -1;
 }
 
@@ -832,23 +757,13 @@ hipError_t launch_skinny(const SkinnyParams& p, hipStream_t s) {
     if (p.am_lp && (p.ymode != YMODE_ARGMAX || (p.am_lp != 1 && p.am_lp != 2) || !p.am_lse || !p.am_side || p.am_eos < 0 || p.am_eos >= p.N ||
                     (p.am_lp == 2 && (p.am_ns < 0 || p.am_ns >= p.N))))
         return hipErrorInvalidValue;
-    if (p.B <= 2) return skinny_launch_cfg<2, 4, 4>(p, s);
-    if (p.B <= 4) return skinny_launch_cfg<4, 4, 4>(p, s);
-    if (p.B <= 8) return skinny_launch_cfg<8, 4, 4>(p, s);
-    if (skinny_sample_wide(p)) {
-        SkinnyPlan pl;
-        const hipError_t e = skinny_plan<16, 2, 4>(p, &pl);
-        return e == hipSuccess ? skinny_sample_launch<16, 2, 4>(p, pl, s) : e;
-    }
-    return skinny_launch_cfg<16, 2, 8>(p, s);  // 16 rows: half-width K-slices, 8 waves per block
+    if (skinny_sampling(p)) return skinny_for_batch<true>(p.B, [&](auto sh) { return skinny_single<decltype(sh), true>(p, s); });
+    return skinny_for_batch<false>(p.B, [&](auto sh) { return skinny_single<decltype(sh), false>(p, s); });
 }
 
 hipError_t launch_skinny_pair(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s) {
     if (a.B != b.B || a.B < 1 || a.B > 16) return hipErrorInvalidValue;
-    if (a.B <= 2) return skinny_pair_cfg<2, 4, 4>(a, b, s);
-    if (a.B <= 4) return skinny_pair_cfg<4, 4, 4>(a, b, s);
-    if (a.B <= 8) return skinny_pair_cfg<8, 4, 4>(a, b, s);
-    return skinny_pair_cfg<16, 2, 8>(a, b, s);
+    return skinny_for_batch<false>(a.B, [&](auto sh) { return skinny_pair_cfg<decltype(sh)>(a, b, s); });
 }
 
 hipError_t launch_skinny_qkv_hoist(const SkinnyParams& a, const SkinnyParams& b, hipStream_t s) {
@@ -857,10 +772,7 @@ hipError_t launch_skinny_qkv_hoist(const SkinnyParams& a, const SkinnyParams& b,
     // the passenger: a plain GEMV over whole LDS-staged rows
     if (b.ymode != YMODE_PLAIN || b.xmode != XMODE_PLAIN || b.parts || b.X2 || b.x_direct || b.K > 1024 || !b.X || !b.W || !b.Y) return hipErrorInvalidValue;
     if (a.w_half != b.w_half || (a.w_nt != 0) != (b.w_nt != 0)) return hipErrorInvalidValue;
-    if (a.B <= 2) return skinny_hoist_cfg<2, 4, 4>(a, b, s);
-    if (a.B <= 4) return skinny_hoist_cfg<4, 4, 4>(a, b, s);
-    if (a.B <= 8) return skinny_hoist_cfg<8, 4, 4>(a, b, s);
-    return skinny_hoist_cfg<16, 2, 8>(a, b, s);
+    return skinny_for_batch<false>(a.B, [&](auto sh) { return skinny_hoist_cfg<decltype(sh)>(a, b, s); });
 }
 
 // ------------------------------------------------------------------------------------------------ decode attention
@@ -1219,100 +1131,82 @@ __global__ __launch_bounds__(NTHR) void dec_attn_kernel(const DecAttnParams p) {
 #pragma unroll
     for (int g = 0; g < G; ++g) finish_row(g);
 }
+// The instantiation a launch runs.  dec_attn_form chooses it -- the only place that does -- and launch_dec_attn maps it to the kernel.
+struct DecAttnForm {
+    bool nt, kv_half, pipe, alive, slot, anc, qcap;
+    int threads, group;
+};
+// The two block-shape choices, as functions of the load policy and the cache precision (constexpr: the dispatch instantiates the chosen
+// forms only, so an A/B of either is a one-line change here).
+// Half-tile software pipeline (PIPE): measured per cross-attention launch, fp16 caches: batch 16 19.04 -> 18.69 us, batch 8
+// 13.35 -> 12.84 (two splits) / 15.28 -> 13.49 (one); fp32 caches 19.87 vs 19.98 (no gain: a tenth of an iteration is arithmetic
+// there, a fifth with fp16 caches) -- so fp16 caches only, and only the non-temporal forms have it.
+constexpr bool dec_attn_pipe(const bool nt, const bool kv_half) { return kv_half && nt; }
+// fp32 caches: eight-wave blocks (measured per launch, 256 -> 512 threads: cross-attention, two splits 19.5 -> 18.8 us, one split
+// (batch 16) 23.9 -> 19.9; self-attention at 224 / 447 keys 6.6 -> 5.7 / 9.4 -> 8.3; below 128 keys the block works as four waves).
+// (sixteen-wave blocks measured SLOWER than eight: cross-attention 19.2 -> 20.6 us, self-attention at 224 keys 5.9 -> 6.4)
+// (and four keys per stream and iteration stay best in the eight-wave form: U = 2 / 4 / 8 -> 19.9 / 19.8 / 20.1 us cross-attention,
+//  6.3 / 5.8 / 6.0 us self-attention at 224 keys)
+// fp16 caches stay on four-wave blocks -- they already are 32 streams, 8 lanes per key: eight waves = 64 streams measured 18.65 vs 18.6 us
+// at batch 16 and 13.1 vs 13.1 at batch 8 with two splits.
+constexpr int dec_attn_threads(const bool kv_half) { return kv_half ? 256 : 512; }
+
+// variant: WT_ATTN_VARIANT (0 forces default-policy loads, 1 forces non-temporal loads, 2: as the engine asks)
+static hipError_t dec_attn_form(const DecAttnParams& p, const int variant, DecAttnForm* f) {
+    if (p.qh) {   // token-level timestamps: the cross-attention launches of the step graph
+        if (p.group > 1 || p.anc || p.slot_row || p.alive || !p.qh_sel || !p.st || !p.ln_h || p.fixed_len <= 0) return hipErrorInvalidValue;
+    } else if (p.group > 1) {   // beam search, cross attention, grouped form: grid z = utterances, `group` query rows per block
+        if (p.anc || p.alive || p.slot_row || p.B % p.group != 0 || (p.group != 2 && p.group != 4)) return hipErrorInvalidValue;
+    } else if (p.anc) {   // beam search: the self-attention launches of the step graph
+        if (p.n_split != 1 || p.slot_row || p.alive || p.anc_ld < p.s_cap) return hipErrorInvalidValue;
+    }
+    // non-temporal K/V loads: 18.6 vs 20.4 us per medium.en cross-attention launch; default policy only when a whole decode
+    // step fits the Infinity Cache (engine.hip: wt_decoder_begin)
+    f->nt = variant == 2 ? p.nt != 0 : variant != 0;
+    f->kv_half = p.kv_half != 0;
+    f->pipe = dec_attn_pipe(f->nt, f->kv_half);
+    f->threads = dec_attn_threads(f->kv_half);
+    // the skip-finished-rows step graph: non-temporal streaming forms only, others run the plain kernels (the forms above reject it)
+    f->alive = p.alive && f->nt;
+    f->slot = p.slot_row != nullptr;   // continuous mode: the cross-attention launches of the step graph (the engine's own plans only)
+    f->anc = p.anc != nullptr;
+    f->qcap = p.qh != nullptr;
+    f->group = p.group > 1 ? p.group : 1;
+    return hipSuccess;
+}
+
+// The forms of one addressing mode (SLOT, ANC, G, QCAP).  Only what dec_attn_form can choose is compiled: the block shape it gives a
+// (load policy, cache precision), and ALIVE where the mode has it; any other record is an error, not another kernel.
+template <bool SLOT, bool ANC, int G, bool QCAP>
+static hipError_t dec_attn_launch(const DecAttnForm& f, const DecAttnParams& p, hipStream_t s) {
+    return with_flags([&](auto NT, auto KVH, auto PIPE, auto ALIVE, auto WAVES8) {
+        constexpr int NTHR = WAVES8 ? 512 : 256;
+        constexpr bool chosen = PIPE == dec_attn_pipe(NT, KVH) && NTHR == dec_attn_threads(KVH);
+        constexpr bool exists = !ALIVE || (NT && !ANC && G == 1 && !QCAP);
+        if constexpr (!chosen || !exists) return hipErrorInvalidValue;
+        else {
+            hipLaunchKernelGGL((dec_attn_kernel<4, NT, KVH, PIPE, ALIVE, NTHR, SLOT, ANC, G, QCAP>), dim3(p.n_split, p.H, p.B / G), dim3(NTHR), 0, s, p);
+            return hipGetLastError();
+        }
+    }, f.nt, f.kv_half, f.pipe, f.alive, f.threads == 512);
+}
+
 hipError_t launch_dec_attn(const DecAttnParams& p, hipStream_t s) {
-    // A/B override: WT_ATTN_VARIANT=0 forces default-policy loads, 1 forces non-temporal loads (2: as the engine asks).  A function-local
-    // static with an initialiser: latched once, thread-safe (handles of different host threads launch concurrently).
+    // A/B override, see dec_attn_form.  A function-local static with an initialiser: latched once, thread-safe (handles of different
+    // host threads launch concurrently).
     static const int variant = [] {
         const char* e = tuning_env("WT_ATTN_VARIANT");
         return e ? atoi(e) : 2;
     }();
-    const dim3 grid(p.n_split, p.H, p.B);
-    const bool nt = variant == 2 ? p.nt != 0 : variant != 0;
-    // non-temporal K/V loads: 18.6 vs 20.4 us per medium.en cross-attention launch; default policy only when a whole decode
-    // step fits the Infinity Cache (engine.hip: wt_decoder_begin)
-    // half-tile software pipeline (PIPE): measured per cross-attention launch, fp16 caches: batch 16 19.04 -> 18.69 us, batch 8
-    // 13.35 -> 12.84 (two splits) / 15.28 -> 13.49 (one); fp32 caches 19.87 vs 19.98 (no gain: a tenth of an iteration is arithmetic
-    // there, a fifth with fp16 caches) -- so fp16 caches only.  A/B: WT_ATTN_PIPE=0|1 forces it off / on for both.
-    static const int pipe = tuning_env("WT_ATTN_PIPE") ? atoi(tuning_env("WT_ATTN_PIPE")) : -1;
-    // fp32 caches: eight-wave blocks (measured per launch, 256 -> 512 threads: cross-attention, two splits 19.5 -> 18.8 us, one split
-    // (batch 16) 23.9 -> 19.9; self-attention at 224 / 447 keys 6.6 -> 5.7 / 9.4 -> 8.3; below 128 keys the block works as four waves).
-    // A/B: WT_ATTN_THREADS=256|512.
-    static const int threads = tuning_env("WT_ATTN_THREADS") ? atoi(tuning_env("WT_ATTN_THREADS")) : 512;
-    // (sixteen-wave blocks measured SLOWER than eight: cross-attention 19.2 -> 20.6 us, self-attention at 224 keys 5.9 -> 6.4)
-    // (and four keys per stream and iteration stay best in the eight-wave form: U = 2 / 4 / 8 -> 19.9 / 19.8 / 20.1 us cross-attention,
-    //  6.3 / 5.8 / 6.0 us self-attention at 224 keys)
-    if (p.qh) {   // token-level timestamps: the cross-attention launches of the step graph, in the default block shapes of the plain forms
-        if (p.group > 1 || p.anc || p.slot_row || p.alive || !p.qh_sel || !p.st || !p.ln_h || p.fixed_len <= 0) return hipErrorInvalidValue;
-        if (!p.kv_half) {
-            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, false, 1, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, false, 1, true>), grid, dim3(512), 0, s, p);
-        } else {
-            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, false, 1, true>), grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, false, 1, true>), grid, dim3(256), 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.group > 1) {   // beam search, cross attention, grouped form: grid z = utterances, `group` query rows per block
-        if (p.anc || p.alive || p.slot_row || p.B % p.group != 0 || (p.group != 2 && p.group != 4)) return hipErrorInvalidValue;
-        const dim3 gg(p.n_split, p.H, p.B / p.group);
-        if (!p.kv_half) {
-            if (p.group == 2 && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, false, 2>), gg, dim3(512), 0, s, p);
-            else if (p.group == 2) hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, false, 2>), gg, dim3(512), 0, s, p);
-            else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, false, 4>), gg, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, false, 4>), gg, dim3(512), 0, s, p);
-        } else {
-            if (p.group == 2 && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, false, 2>), gg, dim3(256), 0, s, p);
-            else if (p.group == 2) hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, false, 2>), gg, dim3(256), 0, s, p);
-            else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, false, 4>), gg, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, false, 4>), gg, dim3(256), 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.anc) {   // beam search: the self-attention launches of the step graph, same block shapes as the plain forms below
-        if (p.n_split != 1 || p.slot_row || p.alive || p.anc_ld < p.s_cap) return hipErrorInvalidValue;
-        if (!p.kv_half) {
-            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, false, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, false, true>), grid, dim3(512), 0, s, p);
-        } else {
-            if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, false, true>), grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, false, true>), grid, dim3(256), 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (p.slot_row) {   // continuous mode: the cross-attention launches of the step graph (the engine's own plans only)
-        if (!p.kv_half) {
-            if (p.alive && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, true, 512, true>), grid, dim3(512), 0, s, p);
-            else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512, true>), grid, dim3(512), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512, true>), grid, dim3(512), 0, s, p);
-        } else {
-            if (p.alive && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, true, 256, true>), grid, dim3(256), 0, s, p);
-            else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, false, 256, true>), grid, dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((dec_attn_kernel<4, false, true, false, false, 256, true>), grid, dim3(256), 0, s, p);
-        }
-        return hipGetLastError();
-    }
-    if (threads == 512 && !p.kv_half && pipe != 1) {
-        if (p.alive && nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, true, 512>), grid, dim3(512), 0, s, p);
-        else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, false, 512>), grid, dim3(512), 0, s, p);
-        else hipLaunchKernelGGL((dec_attn_kernel<4, false, false, false, false, 512>), grid, dim3(512), 0, s, p);
-        return hipGetLastError();
-    }
-    // (fp16 caches stay on four-wave blocks -- they already are 32 streams, 8 lanes per key: eight waves = 64 streams measured 18.65 vs 18.6 us
-    //  at batch 16 and 13.1 vs 13.1 at batch 8 with two splits)
-    if (p.alive) {   // the skip-finished-rows step graph (non-temporal streaming forms only; others fall through to the plain kernels)
-        if (p.kv_half && nt && pipe != 0) { hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true, true>), grid, dim3(256), 0, s, p); return hipGetLastError(); }
-        if (!p.kv_half && nt && pipe != 1) { hipLaunchKernelGGL((dec_attn_kernel<4, true, false, false, true>), grid, dim3(256), 0, s, p); return hipGetLastError(); }
-    }
-    if (p.kv_half) {
-        if (nt && pipe != 0) hipLaunchKernelGGL((dec_attn_kernel<4, true, true, true>), grid, dim3(256), 0, s, p);
-        else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((dec_attn_kernel<4, false, true>), grid, dim3(256), 0, s, p);
-    } else {
-        if (nt && pipe == 1) hipLaunchKernelGGL((dec_attn_kernel<4, true, false, true>), grid, dim3(256), 0, s, p);
-        else if (nt) hipLaunchKernelGGL((dec_attn_kernel<4, true, false>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((dec_attn_kernel<4, false, false>), grid, dim3(256), 0, s, p);
-    }
-    return hipGetLastError();
+    DecAttnForm f;
+    const hipError_t e = dec_attn_form(p, variant, &f);
+    if (e != hipSuccess) return e;
+    if (f.qcap) return dec_attn_launch<false, false, 1, true>(f, p, s);
+    if (f.group == 4) return dec_attn_launch<false, false, 4, false>(f, p, s);
+    if (f.group == 2) return dec_attn_launch<false, false, 2, false>(f, p, s);
+    if (f.anc) return dec_attn_launch<false, true, 1, false>(f, p, s);
+    if (f.slot) return dec_attn_launch<true, false, 1, false>(f, p, s);
+    return dec_attn_launch<false, false, 1, false>(f, p, s);
 }
 
 // ------------------------------------------------------------------------------------------------ greedy select
@@ -2529,10 +2423,13 @@ static hipError_t launch_sample_select(const SelectParams& p, hipStream_t s) {
     memset(&k, 0, sizeof k);
     k.B = p.B; k.N = p.V; k.K = p.samp_K; k.ymode = YMODE_ARGMAX; k.am_samp = 1;
     SkinnyPlan pl;
-    const hipError_t e = p.B <= 2 ? skinny_plan<2, 4, 4>(k, &pl) : p.B <= 4 ? skinny_plan<4, 4, 4>(k, &pl) : p.B <= 8 ? skinny_plan<8, 4, 4>(k, &pl)
-                                                                                                      : skinny_plan<16, 2, 4>(k, &pl);
+    int nw = 0;   // waves per workgroup of the sampling shape
+    const hipError_t e = skinny_for_batch<true>(p.B, [&](auto sh) {
+        nw = sh.NW;
+        return skinny_plan<decltype(sh)>(k, &pl);
+    });
     if (e != hipSuccess) return e;
-    const int G = 4 / pl.nsplit;   // every sampling form runs four waves per workgroup
+    const int G = nw / pl.nsplit;
     if (p.samp_parts_cap < pl.grid) return hipErrorInvalidValue;
     SelectParams q = p;
     q.n_parts = pl.grid;
