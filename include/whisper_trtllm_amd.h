@@ -346,7 +346,11 @@ int wt_logmel_create(int device, int n_fft, int hop, int n_mels, int n_frames, c
                      wt_logmel** out);
 void wt_logmel_destroy(wt_logmel* h);
 /* audio f32 [batch][n_in] on the device (n_in samples each; shorter than 30 s = zero-padded, longer = trimmed)
- * -> mel_out f32 [batch][n_mels][n_frames].  Asynchronous on `stream`. */
+ * -> mel_out f32 [batch][n_mels][n_frames].  Asynchronous on `stream`.
+ * Non-finite input follows the reference (np.maximum and ndarray.max propagate NaN): an utterance with a NaN sample, or an Inf one
+ * (Inf - Inf in the DFT, 0 * Inf in the mel projection), comes out NaN in every element, and the other utterances of the batch are
+ * untouched.  Samples are expected within |x| <= 32768 (int16 range): beyond it the float32 power spectrum can overflow where the
+ * reference's float64 one does not. */
 int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, int n_in, float* mel_out, void* stream);
 
 const char* wt_last_error(void);

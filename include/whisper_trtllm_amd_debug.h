@@ -283,6 +283,11 @@ int wt_dbg_token_timestamp_postpass(wt_engine* dec, int which, void* stream);
 size_t wt_dbg_token_timestamp_bytes(const wt_engine* dec);
 /* the resident cross-K rows of one (layer, head) of the decode in flight, widened to float: HOST f32 [rows][S][64].  Synchronises. */
 int wt_dbg_cross_k_head(wt_engine* dec, int layer, int head, float* out_host, void* stream);
+/* the stages of the log-mel front-end that wt_logmel_forward does not return, as its last call on `h` with this `batch` left them:
+ * pw_out f32 [batch][n_frames][npw], the fp64-DFT power spectrum (columns >= n_bins are 0), and logmel_out f32
+ * [batch][n_frames][n_mels], log10(max(1e-10, mel)) before the max - 8 clamp and the (x + 4) / 4 scaling.  Either may be NULL.  Two
+ * device-to-device copies on `stream` (the stream of that forward), no kernel.  WT_E_INVALID when batch exceeds the handle's workspace. */
+int wt_dbg_logmel_stages(wt_logmel* h, int batch, float* pw_out, float* logmel_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -39,7 +39,7 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_sample_select_scratch_bytes", "wt_dbg_sample_select",
                  "wt_dbg_decode_attention_state_scratch_bytes", "wt_dbg_decode_attention_state",
                  "wt_dbg_self_attention_then_pair_state_scratch_bytes", "wt_dbg_self_attention_then_pair_state",
-                 "wt_dbg_skinny_qkv_hoist", "wt_dbg_skinny_pair_hoisted"]
+                 "wt_dbg_skinny_qkv_hoist", "wt_dbg_skinny_pair_hoisted", "wt_dbg_logmel_stages"]
 
 
 class TensorDesc(Structure):
@@ -228,6 +228,7 @@ def load():
     lib.wt_dbg_self_attention_then_pair_state.argtypes = [P, P, P, P, P, P, P, P, P, P, P, POINTER(c_int32), I, I, I, I, I, I, P, P]
     lib.wt_dbg_skinny_qkv_hoist.argtypes = [P, P, P, P, P, P, P, P, POINTER(c_int32), P, P, P, I, I, I, I, I, I, F, P, P]
     lib.wt_dbg_skinny_pair_hoisted.argtypes = [P, P, P, P, P, P, P, P, P, I, I, I, P]
+    lib.wt_dbg_logmel_stages.argtypes = [c_void_p, I, P, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

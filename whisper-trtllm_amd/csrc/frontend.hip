@@ -5,6 +5,7 @@
 // Framing + windowed DFT + power run in fp64 on the matrix cores (dft_power_f64_kernel), the mel projection on the fp32 MFMA GEMM
 // (gemm_f32_kernel); log/max and the normalising transpose are small coalesced kernels.
 #include "../../include/whisper_trtllm_amd.h"
+#include "../../include/whisper_trtllm_amd_debug.h"
 #include "wt_common.h"
 
 #include <math.h>
@@ -115,7 +116,12 @@ __global__ __launch_bounds__(256) void dft_power_f64_kernel(const float* __restr
             }
 }
 
-// mel[m][c] -> log10(max(1e-10, mel)) in place + per-block maximum (one block = 64 frames of one utterance)
+// Maximum that keeps a NaN once seen (np.maximum / ndarray.max of the reference; fmaxf would drop it): `b > a` is false for a NaN
+// `a`, which therefore stays, and `b != b` takes a NaN `b`.  Finite operands give fmaxf's result.
+__device__ __forceinline__ float max_keep_nan(const float a, const float b) { return (b > a || b != b) ? b : a; }
+
+// mel[m][c] -> log10(max(1e-10, mel)) in place + per-block maximum (one block = 64 frames of one utterance); a NaN mel stays NaN
+// and makes the block's maximum NaN
 __global__ __launch_bounds__(256) void log_max_kernel(float* __restrict__ mel, float* __restrict__ bmax, int T, int n_mels) {
     __shared__ float red[4];
     const int b = blockIdx.y, t0 = blockIdx.x * 64;
@@ -123,18 +129,20 @@ __global__ __launch_bounds__(256) void log_max_kernel(float* __restrict__ mel, f
     const int n = min(64, T - t0) * n_mels;
     float* base = mel + ((size_t)b * T + t0) * n_mels;
     for (int i = threadIdx.x; i < n; i += 256) {
-        const float v = log10f(fmaxf(1e-10f, base[i]));
+        const float x = base[i];
+        const float v = log10f(x < 1e-10f ? 1e-10f : x);   // false for NaN: it goes through the log
         base[i] = v;
-        mx = fmaxf(mx, v);
+        mx = max_keep_nan(mx, v);
     }
 #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    for (int o = 32; o >= 1; o >>= 1) mx = max_keep_nan(mx, __shfl_xor(mx, o));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     __syncthreads();
-    if (threadIdx.x == 0) bmax[(size_t)b * gridDim.x + blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    if (threadIdx.x == 0)
+        bmax[(size_t)b * gridDim.x + blockIdx.x] = max_keep_nan(max_keep_nan(red[0], red[1]), max_keep_nan(red[2], red[3]));
 }
 
-// out[b][c][t] = (max(logmel[b][t][c], utterance_max - 8) + 4) / 4
+// out[b][c][t] = (max(logmel[b][t][c], utterance_max - 8) + 4) / 4; a NaN utterance maximum makes every element of the utterance NaN
 __global__ __launch_bounds__(256) void normalize_transpose_kernel(const float* __restrict__ mel, const float* __restrict__ bmax,
                                                                   int nblk, float* __restrict__ out, int T, int n_mels) {
     __shared__ float tile[64][129];
@@ -142,9 +150,9 @@ __global__ __launch_bounds__(256) void normalize_transpose_kernel(const float* _
     const int b = blockIdx.y, t0 = blockIdx.x * 64;
     if (threadIdx.x < 64) {
         float mx = -INFINITY;
-        for (int i = threadIdx.x; i < nblk; i += 64) mx = fmaxf(mx, bmax[(size_t)b * nblk + i]);
+        for (int i = threadIdx.x; i < nblk; i += 64) mx = max_keep_nan(mx, bmax[(size_t)b * nblk + i]);
 #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        for (int o = 32; o >= 1; o >>= 1) mx = max_keep_nan(mx, __shfl_xor(mx, o));
         if (threadIdx.x == 0) s_max = mx;
     }
     const int nt = min(64, T - t0);
@@ -154,7 +162,10 @@ __global__ __launch_bounds__(256) void normalize_transpose_kernel(const float* _
     const float floor_v = s_max - 8.0f;
     for (int i = threadIdx.x; i < n_mels * 64; i += 256) {
         const int c = i >> 6, tl = i & 63;
-        if (tl < nt) out[((size_t)b * n_mels + c) * T + t0 + tl] = (fmaxf(tile[tl][c], floor_v) + 4.0f) * 0.25f;
+        if (tl < nt) {
+            const float v = tile[tl][c];
+            out[((size_t)b * n_mels + c) * T + t0 + tl] = ((v >= floor_v ? v : floor_v) + 4.0f) * 0.25f;   // NaN floor: false, NaN out
+        }
     }
 }
 
@@ -254,5 +265,20 @@ extern "C" int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, in
     hipLaunchKernelGGL(normalize_transpose_kernel, dim3(nblk, batch), dim3(256), 0, s, h->mel, h->bmax, nblk, mel_out, T, h->n_mels);
     e = hipGetLastError();
     if (e != hipSuccess) return wt_set_error(WT_E_HIP, "front-end kernel launch failed: %s", hipGetErrorString(e));
+    return WT_OK;
+}
+
+// test hook (whisper_trtllm_amd_debug.h): the intermediate buffers of the last wt_logmel_forward of `batch` utterances
+extern "C" int wt_dbg_logmel_stages(wt_logmel* h, int batch, float* pw_out, float* logmel_out, void* stream) {
+    if (!h || batch < 1 || batch > h->cap) return wt_set_error(WT_E_INVALID, "wt_dbg_logmel_stages: batch %d outside the workspace", batch);
+    wt::DeviceGuard guard(h->device);
+    if (guard.err != hipSuccess) return wt_set_error(WT_E_HIP, "hipSetDevice failed");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t M = (size_t)batch * h->n_frames;
+    // the workspace may be laid out for a larger batch than this one: pw and mel each start at their own base, rows are contiguous
+    if (pw_out && hipMemcpyAsync(pw_out, h->pw, M * h->npw * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return wt_set_error(WT_E_HIP, "wt_dbg_logmel_stages: copy of the power spectrum failed");
+    if (logmel_out && hipMemcpyAsync(logmel_out, h->mel, M * h->n_mels * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return wt_set_error(WT_E_HIP, "wt_dbg_logmel_stages: copy of the log-mel failed");
     return WT_OK;
 }
