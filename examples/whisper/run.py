@@ -70,6 +70,10 @@ def parse_arguments():
                         "then decode the utterances whose transcript is repetitive (compression ratio > 2.4) or unlikely (avg_logprob < -1) "
                         "again at temperature 0.2, 0.4 .. 1.0 (not those whose no_speech_prob > 0.6, with --no_speech_token_id); implies "
                         "--return_logprobs; prints the temperature used per utterance")
+    parser.add_argument("--prompt_ids", type=int, nargs="+", default=None, metavar="N", help="fast path: a decoder prompt in front of the "
+                        "transcript, shared by every utterance -- token ids, the first of them <|startofprev|> (previous text / "
+                        "initial_prompt; text -> ids is the caller's: there is no BPE encoder here); needs a batch plan, an fp32 decoder "
+                        "engine, no beams and no --return_token_timestamps")
     parser.add_argument("--length_penalty", type=float, default=1.0)
     parser.add_argument("--early_stopping", action="store_true")
     args = parser.parse_args()
@@ -91,6 +95,10 @@ def parse_arguments():
         parser.error("--return_logprobs needs the fast path with a batch plan (--batching sorted | dataset) and no beams")
     if args.no_speech_token_id is not None and not args.return_logprobs:
         parser.error("--no_speech_token_id needs --return_logprobs")
+    if args.prompt_ids is not None and (args.batching == "continuous" or args.num_beams > 1 or args.return_token_timestamps or args.session
+                                        or args.compare or args.engine_precision != "float32"):
+        parser.error("--prompt_ids needs the fast path with a batch plan (--batching sorted | dataset) and an fp32 decoder engine: no beams, "
+                     "no --return_token_timestamps, no --session / --compare (the Session path takes no prompt)")
     if args.alignment_heads is not None:
         try:
             args.alignment_heads = [tuple(int(x) for x in pair.split(",")) for pair in args.alignment_heads]
@@ -240,6 +248,8 @@ if __name__ == "__main__":
                 if args.temperature_fallback:
                     kw = [{"return_timestamps": args.return_timestamps, "no_speech_token_id": args.no_speech_token_id,
                            "temperature_fallback": {"seeds": [args.seed + i for i in g]}} for g in groups]
+                if args.prompt_ids is not None:      # generate / generate_with_fallback(prompt_ids=...): one prompt for every utterance
+                    kw = [dict(k, prompt_ids=args.prompt_ids) for k in (kw or [{}] * len(groups))]
                 if args.num_beams > 1:
                     kw = [{"num_beams": args.num_beams, "length_penalty": args.length_penalty, "early_stopping": args.early_stopping}] * len(groups)
                 for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):

@@ -291,6 +291,32 @@ typedef struct {
 } wt_sampling_params;
 int wt_decoder_set_sampling(wt_engine* dec, const wt_sampling_params* p);
 
+/* (9g) decoder prompts (transformers' generate(prompt_ids=...), openai-whisper's initial_prompt / condition_on_previous_text): `len`
+ * tokens in front of decoder_start_token_id, the first of them <|startofprev|>.  Row b of the id buffer then starts as
+ * prompt[b][0..len), decoder_start_token_id, and wt_decoder_begin runs positions 0..len-1 of every row through all decoder layers in
+ * ONE pass, the prefill: GEMMs over batch * len rows and a causal attention kernel instead of len dependent decode steps.  It writes
+ * the prompt's keys and values into rows 0..len-1 of the resident self caches and leaves the decode at cur_len = len + 1 with the start
+ * token at position len as the input of step 0; no vocabulary projection runs for prompt positions.  The step loop is what it was:
+ * every rule keys on the absolute sequence length, so ALL positions of wt_greedy_params and wt_timestamp_params (begin_index,
+ * forced_decoder_ids, the timestamp rules' begin_index) stay absolute sequence positions -- the caller shifts them by len -- and
+ * max_length counts the prompt, as in transformers.  Step 0 is still the step whose input is the start token: no_speech_prob (9e) keeps
+ * its meaning, sampling (9f) draws at the absolute positions.  wt_decoder_read_ids returns whole rows, prompt included; the
+ * log-probability entries (9e) of positions 0..len are 0.
+ * ids: host pointer, row-major [n_rows][len], copied by the call.  n_rows == 1: every row of the next decode uses row 0; else n_rows
+ * must be >= that decode's batch.  One prompt length per call.
+ * The setting applies from the next wt_decoder_begin on this handle; p == NULL or len <= 0 turns it off, and wt_decoder_begin then
+ * enqueues exactly what it did before.  WT_E_INVALID for a token outside the vocabulary; wt_decoder_begin returns WT_E_INVALID when
+ * n_rows is neither 1 nor >= its batch or when len + 2 > max_length, and refuses (WT_E_UNSUPPORTED) a prompt on an fp16 decoder engine,
+ * together with beam search (9c) and together with token-level timestamps (9d: their history is indexed by step and sized by the
+ * sequence length); wt_decoder_stream_begin refuses (WT_E_UNSUPPORTED) while a prompt is set.  It combines with the timestamp mode
+ * (9b), the log-probability mode (9e) and sampling (9f). */
+typedef struct {
+    const int32_t* ids;   /* host, row-major [n_rows][len]; copied by the call */
+    int32_t n_rows;       /* 1: every row of the next decode uses row 0; else must be >= that decode's batch */
+    int32_t len;          /* tokens placed BEFORE decoder_start_token_id, 0 < len */
+} wt_prompt_params;
+int wt_decoder_set_prompt(wt_engine* dec, const wt_prompt_params* p);   /* NULL or len <= 0: off */
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

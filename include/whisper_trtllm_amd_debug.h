@@ -288,6 +288,17 @@ int wt_dbg_cross_k_head(wt_engine* dec, int layer, int head, float* out_host, vo
  * [batch][n_frames][n_mels], log10(max(1e-10, mel)) before the max - 8 clamp and the (x + 4) / 4 scaling.  Either may be NULL.  Two
  * device-to-device copies on `stream` (the stream of that forward), no kernel.  WT_E_INVALID when batch exceeds the handle's workspace. */
 int wt_dbg_logmel_stages(wt_logmel* h, int batch, float* pw_out, float* logmel_out, void* stream);
+/* prefill_attn_kernel alone (kernels_prefill.hip): ctx [B][nq][ldc] = softmax(q_scale . q k^T) v per head, q device f32 [B][nq][ldq] with
+ * head h at column 64 h, kcache / vcache device f32 [B][H][cap][64] of which keys [0, nk) are read.  causal 1: query t sees keys 0..t and
+ * nk must equal nq; 0: every query sees all nk keys.  ldq / ldc multiples of 4, >= 64 H. */
+int wt_dbg_prefill_attention(const float* q, const float* kcache, const float* vcache, float* ctx, int B, int H, int nq, int nk, int cap, int ldq,
+                             int ldc, int causal, float q_scale, void* stream);
+/* the prefill's query finish alone: q [rows][d] = (u - mean(h1) . r) * rstd(h1) + t per row (what dec_attn_kernel does to its folded
+ * query); u / h1 / q device f32 [rows][d], r / t device f32 [d], d <= 1280 */
+int wt_dbg_prefill_query_finish(const float* u, const float* h1, const float* r, const float* t, float* q, int rows, int d, void* stream);
+/* the resident self-K (which = 0) or self-V (1) rows of one (layer, head) of the decode in flight: HOST f32 [rows][max_target_positions][64],
+ * rows the decode has not written hold whatever the cache held.  fp32 decoder engines only.  Synchronises. */
+int wt_dbg_self_kv_head(wt_engine* dec, int layer, int head, int which, float* out_host, void* stream);
 
 #ifdef __cplusplus
 }

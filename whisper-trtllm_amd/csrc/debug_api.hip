@@ -899,3 +899,16 @@ extern "C" int wt_dbg_token_timestamp_dtw(const float* matrix, int B, int N, int
     p.path = path_out; p.path_len = path_len; p.out = ts_out; p.out_ld = N + 1;
     return rc_of(launch_tt_dtw(p, (hipStream_t)stream));
 }
+
+// ---- the prefill's own kernels (kernels_prefill.hip), as wt_decoder_begin launches them behind a prompt ----
+extern "C" int wt_dbg_prefill_attention(const float* q, const float* kcache, const float* vcache, float* ctx, int B, int H, int nq, int nk, int cap,
+                                        int ldq, int ldc, int causal, float q_scale, void* stream) {
+    PrefillAttnParams a;
+    memset(&a, 0, sizeof a);
+    a.q = q; a.k = kcache; a.v = vcache; a.ctx = ctx; a.B = B; a.H = H; a.nq = nq; a.nk = nk; a.cap = cap; a.ldq = ldq; a.ldc = ldc;
+    a.causal = causal ? 1 : 0; a.q_scale = q_scale;
+    return rc_of(launch_prefill_attention(a, (hipStream_t)stream));
+}
+extern "C" int wt_dbg_prefill_query_finish(const float* u, const float* h1, const float* r, const float* t, float* q, int rows, int d, void* stream) {
+    return rc_of(launch_prefill_query_finish(u, h1, r, t, q, rows, d, (hipStream_t)stream));
+}

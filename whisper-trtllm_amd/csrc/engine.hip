@@ -191,6 +191,12 @@ struct wt_engine {
     uint8_t* tt_trace = nullptr;
     int tt_rows = 0, tt_steps = 0;   // q_hist / matrix dimensions of the decode in flight: rows = B, steps = max_length - 1
     std::vector<int> tt_h_sel;    // host image of tt_sel
+    // decoder prompt (wt_decoder_set_prompt): the ids asked for (applied by the next wt_decoder_begin; len 0: off), the prompt length of the
+    // decode in flight, and the prefill's workspace (allocated by the first prompt decode, grown when needed)
+    std::vector<int> prompt_req;   // [prompt_req_rows][prompt_req_len]
+    int prompt_req_rows = 0, prompt_req_len = 0, prompt_len = 0;
+    char* pf_ws = nullptr;
+    size_t pf_bytes = 0;
     hipStream_t own_stream = nullptr;
     // step graphs: [0] every row attends (the only one a decode without early finishers ever replays), [1] finished rows stream no K/V,
     // [2] / [3] the same two for the continuous mode (per-slot cross-cache rows, stream_finish_kernel)
@@ -269,6 +275,7 @@ extern "C" void wt_engine_close(wt_engine* e) {
     if (e->enc_ws) hipFree(e->enc_ws);
     if (e->dec_ws) hipFree(e->dec_ws);
     if (e->tt_buf) hipFree(e->tt_buf);
+    if (e->pf_ws) hipFree(e->pf_ws);
     e->weights.reset();   // the last handle sharing the payload frees it
     delete e;
 }
@@ -1233,6 +1240,96 @@ extern "C" int wt_decoder_set_sampling(wt_engine* e, const wt_sampling_params* p
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_prompt(wt_engine* e, const wt_prompt_params* p) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_prompt: not a decoder engine");
+    if (!p || p->len <= 0) {
+        e->prompt_req.clear();
+        e->prompt_req_rows = e->prompt_req_len = 0;
+        return WT_OK;
+    }
+    if (!p->ids || p->n_rows < 1) return fail(WT_E_INVALID, "wt_decoder_set_prompt: null ids or %d rows", p->n_rows);
+    if (p->len >= e->T) return fail(WT_E_INVALID, "wt_decoder_set_prompt: %d prompt tokens >= max_target_positions %d", p->len, e->T);
+    const size_t n = (size_t)p->n_rows * p->len;
+    for (size_t i = 0; i < n; ++i)
+        if (p->ids[i] < 0 || p->ids[i] >= e->V)
+            return fail(WT_E_INVALID, "wt_decoder_set_prompt: token %d (row %zu, position %zu) outside the vocabulary", p->ids[i], i / p->len, i % p->len);
+    e->prompt_req.assign(p->ids, p->ids + n);
+    e->prompt_req_rows = p->n_rows;
+    e->prompt_req_len = p->len;
+    return WT_OK;
+}
+
+// The prefill (DESIGN.md "Decoder prompts"): positions 0..len-1 of all B rows through the decoder layers in one pass over M = B * len rows
+// (utterance-major), leaving their keys and values in rows 0..len-1 of the resident self caches.  The kernels are the encoder's
+// (launch_layernorm, launch_gemm_f32) and kernels_prefill.hip's; the cross K/V of this decode must be enqueued on `s` before.  The last
+// layer stops behind its k|v projection: nothing reads a prompt position's output (no vocabulary projection runs for it).
+static int prefill_reserve(wt_engine* e, int B, int len, hipStream_t s, float** bufs, int** ids_dev) {
+    const size_t M = (size_t)B * len, d = e->d;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
+    // h, h1, x, q: [M][d]; ah: [M][2d] (self-attention context | layer input); ffn: [M][F]; the prompt ids
+    const size_t o_h = take(M * d * 4), o_h1 = take(M * d * 4), o_x = take(M * d * 4), o_q = take(M * d * 4), o_ah = take(M * 2 * d * 4);
+    const size_t o_f = take(M * e->F * 4), o_ids = take((size_t)MAX_ROWS * e->T * 4);
+    if (off > e->pf_bytes) {
+        HIPCHK(hipStreamSynchronize(s));   // nothing of an earlier decode may still use the old buffer
+        if (e->pf_ws) { hipFree(e->pf_ws); e->pf_ws = nullptr; e->pf_bytes = 0; }
+        hipError_t he = hipMalloc((void**)&e->pf_ws, off);
+        if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for the prompt prefill workspace failed: %s", off, hipGetErrorString(he));
+        e->pf_bytes = off;
+    }
+    char* b = e->pf_ws;
+    bufs[0] = (float*)(b + o_h); bufs[1] = (float*)(b + o_h1); bufs[2] = (float*)(b + o_x); bufs[3] = (float*)(b + o_q);
+    bufs[4] = (float*)(b + o_ah); bufs[5] = (float*)(b + o_f);
+    *ids_dev = (int*)(b + o_ids);
+    return WT_OK;
+}
+
+static int enqueue_prefill(wt_engine* e, int B, int len, float* const* bufs, const int* ids_dev, int n_rows, hipStream_t s) {
+    const int d = e->d, H = e->H, M = B * len;
+    float *h = bufs[0], *h1 = bufs[1], *x = bufs[2], *q = bufs[3], *ah = bufs[4], *ffn = bufs[5];
+    int rc;
+    auto dense = [&](const float* A, int lda, int K, const float* Wt, const float* bias, int N, float* Cout, int act, const float* resid) {
+        GemmParams g;
+        memset(&g, 0, sizeof g);
+        g.A = A; g.lda = lda; g.a_rows_per_batch = M; g.W = Wt; g.bias = bias; g.M = M; g.N = N; g.K = K; g.act = act;
+        g.C = Cout; g.ldc = N; g.c_rows_per_batch = M; g.resid = resid;
+        return timed_gemm(e, g, s);
+    };
+    LAUNCH(launch_prefill_embed(ids_dev, n_rows, len, e->tok_emb, e->pos_emb, h, B, d, s));
+    for (int i = 0; i < e->L; ++i) {
+        const DecLayerW& l = e->dec_layers[i];
+        const size_t self_layer = (size_t)i * B * H * e->T * HEAD_DIM, cross_layer = (size_t)i * e->cross_rows * H * e->S * HEAD_DIM;
+        float *sk = e->self_k + self_layer, *sv = e->self_v + self_layer;
+        LAUNCH(launch_layernorm(h, l.ln1_w, l.ln1_b, x, M, d, s));
+        {   // k|v: rows [d, 3d) of qkv_w, split by head straight into cache rows [0, len) of every utterance (the cross-K/V projection's epilogue)
+            GemmParams g = cross_kv_gemm_params(x, len, l.qkv_w + (size_t)d * d, l.qkv_b + d, sk, sv, 4, B, len, H, e->T, 0, 0);
+            if ((rc = timed_gemm(e, g, s))) return rc;
+        }
+        if (i == e->L - 1) break;
+        if ((rc = dense(x, d, d, l.qkv_w, l.qkv_b, d, q, 0, nullptr))) return rc;
+        PrefillAttnParams a;
+        memset(&a, 0, sizeof a);
+        a.q = q; a.k = sk; a.v = sv; a.ctx = ah; a.B = B; a.H = H; a.nq = len; a.nk = len; a.cap = e->T; a.ldq = d; a.ldc = 2 * d;
+        a.causal = 1; a.q_scale = 0.125f;
+        LAUNCH(launch_prefill_attention(a, s));
+        // [a ; h] side by side: the folded query multiplies both (the blob holds fold_w as one [d][2d] matrix)
+        HIPCHK(hipMemcpy2DAsync(ah + d, (size_t)2 * d * 4, h, (size_t)d * 4, (size_t)d * 4, M, hipMemcpyDeviceToDevice, s));
+        if ((rc = dense(ah, 2 * d, d, l.o_w, l.o_b, d, h1, 0, h))) return rc;                       // h1 = h + Wo.a + bo
+        if ((rc = dense(ah, 2 * d, 2 * d, l.fold_w, l.fold_c, d, q, 0, nullptr))) return rc;        // u = fold_w.[a ; h] + fold_c
+        LAUNCH(launch_prefill_query_finish(q, h1, l.fold_r, l.fold_t, q, M, d, s));
+        memset(&a, 0, sizeof a);
+        a.q = q; a.k = e->cross_k + cross_layer; a.v = e->cross_v + cross_layer; a.ctx = x; a.B = B; a.H = H; a.nq = len; a.nk = e->S; a.cap = e->S;
+        a.ldq = d; a.ldc = d; a.causal = 0; a.q_scale = 1.f;
+        LAUNCH(launch_prefill_attention(a, s));
+        if ((rc = dense(x, d, d, l.co_w, l.co_b, d, h1, 0, h1))) return rc;
+        LAUNCH(launch_layernorm(h1, l.ln3_w, l.ln3_b, x, M, d, s));
+        if ((rc = dense(x, d, d, l.fc1_w, l.fc1_b, e->F, ffn, 1, nullptr))) return rc;
+        if ((rc = dense(ffn, e->F, e->F, l.fc2_w, l.fc2_b, d, h1, 0, h1))) return rc;
+        std::swap(h, h1);
+    }
+    return WT_OK;
+}
+
 // the log-probability setting of the decode that is starting (a changed one re-captures the step graphs)
 static void lp_apply(wt_engine* e, const wt_logprob_params lp) {
     if (memcmp(&e->lp_cur, &lp, sizeof lp) != 0) e->graph_valid = false;
@@ -1259,6 +1356,18 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
             return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and temperature sampling cannot be combined");
         if (U * nb > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", U, nb, MAX_ROWS);
         B = U * nb;
+    }
+    const int plen = e->prompt_req_len, prows = e->prompt_req_rows;
+    if (plen > 0) {
+        if (e->w_half || e->kv_esz != 4)
+            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: decoder prompts need an fp32 decoder engine (the prefill's GEMMs and attention are fp32)");
+        if (nb > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and beam search cannot be combined");
+        if (e->tt_req.n_sel > 0)
+            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and token-level timestamps cannot be combined (their query history is "
+                                          "indexed by step and sized by the sequence length)");
+        if (prows != 1 && prows < B) return fail(WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_prompt gave %d prompt rows for a batch of %d", prows, B);
+        if (plen + 2 > p->max_length)
+            return fail(WT_E_INVALID, "wt_decoder_begin: %d prompt tokens + the start token + one generated token > max_length %d", plen, p->max_length);
     }
     const float samp_temp = e->samp_req_temp;
     if (samp_temp > 0.f && e->samp_req_list && (int)e->samp_req_seeds.size() < B)
@@ -1296,10 +1405,24 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
         fill_select_params(e, sp);
         LAUNCH(launch_beam_init(sp, s));
     }
+    float* pf_bufs[6];
+    int* pf_ids = nullptr;
+    if (plen > 0) {   // the prompt's ids and the state behind it; the step-0 input below is then the start token at position plen
+        rc = prefill_reserve(e, B, plen, s, pf_bufs, &pf_ids);
+        if (rc) return rc;
+        // (pageable source kept alive by the handle, as the sampling seeds above)
+        HIPCHK(hipMemcpyAsync(pf_ids, e->prompt_req.data(), (size_t)(prows == 1 ? 1 : B) * plen * 4, hipMemcpyHostToDevice, s));
+        LAUNCH(launch_prefill_state(e->st, e->ids, pf_ids, prows == 1 ? 1 : B, plen, B, p->max_length, p->decoder_start_token_id, s));
+    }
+    e->prompt_len = plen;
     LAUNCH(launch_dec_embed(e->ids, p->max_length, e->tok_emb, e->pos_emb, e->dh, B, e->d, e->st, s, e->w_half));  // input of step 0
     // the beams of an utterance attend over the same encoder memory: its cross K/V are projected once, into cache row u
     rc = cross_kv_project(e, enc_hidden, U, e->S, 0, e->cross_k, e->cross_v, e->kv_esz, s, e->cross_rows, 0);
     if (rc) return rc;
+    if (plen > 0) {   // behind the cross K/V projection: the prefill's cross attention reads this decode's cross caches
+        rc = enqueue_prefill(e, B, plen, pf_bufs, pf_ids, prows == 1 ? 1 : B, s);
+        if (rc) return rc;
+    }
     e->begun = true;
     return WT_OK;
 }
@@ -1432,6 +1555,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
     if (e->tt_req.n_sel > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token-level timestamps are a batch-decode feature (wt_decoder_begin)");
     if (e->lp_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token log-probabilities are a batch-decode feature (wt_decoder_begin)");
     if (e->samp_req_temp > 0.f) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: temperature sampling is a batch-decode feature (wt_decoder_begin)");
+    if (e->prompt_req_len > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: decoder prompts are a batch-decode feature (wt_decoder_begin)");
     if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);
@@ -1615,7 +1739,7 @@ extern "C" int wt_decoder_run(wt_engine* e, int lookahead, int* cur_len, int* n_
     hipStream_t s = (hipStream_t)stream;
     if (lookahead <= 0) lookahead = e->nt_loads ? 1 : 3;   // small models: a step is 0.15-0.3 ms, keep more of them queued
     if (lookahead > 64) lookahead = 64;
-    const int max_steps = e->max_length - 1;               // MaxLengthCriteria fires at the latest after this many steps
+    const int max_steps = e->max_length - 1 - e->prompt_len;   // MaxLengthCriteria fires at the latest after this many steps
     unsigned long long mb = 0;
     int spins = 0, slices = 0;   // since the last launch: busy-wait iterations, then 20 us sleep slices
     for (;;) {
@@ -1797,6 +1921,22 @@ extern "C" int wt_dbg_cross_k_head(wt_engine* e, int layer, int head, float* out
         if (e->kv_esz == 4) memcpy(out_host + b * n, tmp.data(), n * 4);
         else for (size_t i = 0; i < n; ++i) out_host[b * n + i] = (float)((const _Float16*)tmp.data())[i];
     }
+    return WT_OK;
+}
+
+// the resident self-K / self-V rows of one (layer, head): [B][T][64] -- host staging, synchronises
+extern "C" int wt_dbg_self_kv_head(wt_engine* e, int layer, int head, int which, float* out_host, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->stream_mode) return fail(WT_E_STATE, "wt_dbg_self_kv_head: no batch decode in flight");
+    if (!out_host || layer < 0 || layer >= e->L || head < 0 || head >= e->H || (which != 0 && which != 1))
+        return fail(WT_E_INVALID, "wt_dbg_self_kv_head: bad arguments");
+    if (e->kv_esz != 4) return fail(WT_E_UNSUPPORTED, "wt_dbg_self_kv_head: fp32 decoder engines only");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    const size_t n = (size_t)e->T * HEAD_DIM;
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    const float* cache = which ? e->self_v : e->self_k;
+    for (int b = 0; b < e->B; ++b)
+        HIPCHK(hipMemcpy(out_host + b * n, cache + (((size_t)layer * e->B + b) * e->H + head) * n, n * 4, hipMemcpyDeviceToHost));
     return WT_OK;
 }
 

@@ -160,6 +160,28 @@ struct DecAttnParams {
     int qh_rows, qh_steps;
 };
 
+// ---- prefill attention (query length nq; kernels_prefill.hip): the prompt positions of a decode through one decoder layer together ----
+struct PrefillAttnParams {
+    const float* q;        // [B][nq][ldq], head h at column 64 h (not scaled: q_scale below)
+    const float* k;        // head cache [rows >= B][H][cap][64], utterance b in cache row b; only keys [0, nk) are read
+    const float* v;
+    float* ctx;            // [B][nq][ldc], head h at column 64 h
+    int B, H, nq, nk, cap;
+    int ldq, ldc;          // multiples of 4, >= 64 H
+    int causal;            // 1: query t sees keys 0..t (nk == nq); 0: every query sees keys 0..nk-1
+    float q_scale;
+};
+hipError_t launch_prefill_attention(const PrefillAttnParams& p, hipStream_t s);
+// q[m] = (u[m] - mean(h1[m]) . r) * rstd(h1[m]) + t over `rows` rows of d <= 1280: the folded cross-attention query finished as
+// dec_attn_kernel finishes it (DecAttnParams.ln_h / ln_r / ln_t); q may alias u
+hipError_t launch_prefill_query_finish(const float* u, const float* h1, const float* r, const float* t, float* q, int rows, int d, hipStream_t s);
+// x[b * len + t] = embed_tokens[prompt(b)[t]] + embed_positions[t]; prompt [n_rows][len] on the device, n_rows == 1: shared by all rows
+hipError_t launch_prefill_embed(const int* prompt, int n_rows, int len, const float* tok_emb, const float* pos_emb, float* x, int B, int d,
+                                hipStream_t s);
+// behind launch_dec_init: ids row b = prompt(b), start token; cur_len = len + 1, pos = len, self_len = len for every row
+hipError_t launch_prefill_state(DecState* st, int* ids, const int* prompt, int n_rows, int len, int B, int max_length, int start_token,
+                                hipStream_t s);
+
 // ---- token-level timestamps: the post-pass over the captured queries and the resident cross-K cache (kernels_token_timestamps.hip) ----
 // Per utterance b and selected head: W[t][s] = softmax_s(q_hist[t] . K[s]); W = (W - mean_t) / std_t (population std over the N tokens);
 // a median of odd `width` along s with reflect padding (the input unchanged when S <= width / 2); the mean over the heads = matrix[N][S];

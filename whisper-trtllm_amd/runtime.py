@@ -219,17 +219,55 @@ def _check_beam_args(num_beams, return_timestamps, logits_trace, force_eos_step,
         raise ValueError("beam search does not take logits_trace / force_eos_step(s)")
 
 
+def prompt_rows(prompt_ids, batch: int, max_target_positions: int):
+    """The decoder prompt of a batch as the engine takes it (wt_decoder_set_prompt): `prompt_ids` is a 1-D sequence shared by the batch or a
+    2-D [batch, n] sequence with per-row contents of equal length; the first entry is <|startofprev|>.  The text part is cut to its last
+    max_target_positions // 2 - 1 tokens, as openai-whisper's _get_initial_tokens does.  Returns a list of 1 or `batch` rows."""
+    if hasattr(prompt_ids, "tolist"):
+        prompt_ids = prompt_ids.tolist()
+    rows = list(prompt_ids)
+    if not rows:
+        raise ValueError("prompt_ids is empty (pass None for no prompt)")
+    if not isinstance(rows[0], (list, tuple)):
+        rows = [rows]
+    rows = [[int(t) for t in r] for r in rows]
+    n = len(rows[0])
+    if n < 1 or any(len(r) != n for r in rows):
+        raise ValueError("prompt_ids rows must have one length >= 1 (per-row prompt lengths are not supported)")
+    if len(rows) != 1 and len(rows) != batch:
+        raise ValueError(f"prompt_ids has {len(rows)} rows for a batch of {batch} (one shared row, or one per utterance)")
+    keep = max_target_positions // 2 - 1
+    return [r[:1] + r[1:][-keep:] for r in rows]
+
+
+def _check_prompt_args(rows, vocab_size, max_length, num_beams, return_token_timestamps, half_engine):
+    """What the engine refuses (wt_decoder_set_prompt / wt_decoder_begin: WT_E_INVALID, WT_E_UNSUPPORTED), refused before anything is enqueued."""
+    if half_engine:
+        raise ValueError("prompt_ids needs an fp32 decoder engine (the prefill is fp32)")
+    if num_beams > 1:
+        raise ValueError("prompt_ids and beam search cannot be combined")
+    if return_token_timestamps:
+        raise ValueError("prompt_ids and return_token_timestamps cannot be combined")
+    bad = [t for r in rows for t in r if not 0 <= t < vocab_size]
+    if bad:
+        raise ValueError(f"prompt_ids holds ids outside the vocabulary [0, {vocab_size}): {bad[:4]}")
+    if len(rows[0]) + 2 > max_length:
+        raise ValueError(f"a prompt of {len(rows[0])} tokens, the start token and one generated token exceed max_length {max_length}")
+
+
 class DecodeScores:
     """Confidence signals of a greedy decode (generate(..., return_logprobs=True)), openai-whisper's definitions:
     `token_logprobs` float32 [B, len]: log-probability of every emitted token under the step's processed scores (0 at position 0, at
     forced positions and behind a row's EOS); `sum_logprob` float32 [B]: the row's sum through its EOS; `avg_logprob` float32 [B] =
     sum_logprob / scored positions (generated tokens including the EOS and forced ones; a row without EOS: all len - 1 of them);
-    `no_speech_prob` float32 [B] or None: softmax(raw logits of the first step)[no_speech_token_id]."""
+    `no_speech_prob` float32 [B] or None: softmax(raw logits of the first step)[no_speech_token_id].
+    `prompt_len`: tokens of a decoder prompt in front of the start token; they are not scored (their entries are 0)."""
 
-    def __init__(self, ids, token_logprobs, sum_logprob, no_speech_prob, eos_token_id: int):
+    def __init__(self, ids, token_logprobs, sum_logprob, no_speech_prob, eos_token_id: int, prompt_len: int = 0):
         import torch
         self.token_logprobs, self.sum_logprob, self.no_speech_prob = token_logprobs, sum_logprob, no_speech_prob
-        body = ids[:, 1:]
+        self.prompt_len = prompt_len
+        body = ids[:, prompt_len + 1:]
         is_eos = body == eos_token_id
         width = torch.full((body.shape[0],), body.shape[1], dtype=torch.int64, device=body.device)
         self.n_scored = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, width)
@@ -324,7 +362,9 @@ class WhisperDecoderEngine:
         """Another engine on the same device weights (own resident KV caches, step graphs, mailbox): for a second host thread / stream."""
         return WhisperDecoderEngine(None, self.config, _session=self.session.clone())
 
-    def _params(self, max_length, force_eos_step, logits_trace, force_eos_steps=None, return_timestamps=False):
+    def _params(self, max_length, force_eos_step, logits_trace, force_eos_steps=None, return_timestamps=False, prompt_len=0):
+        """`prompt_len`: tokens of a decoder prompt in front of the start token -- every position of the rules is an absolute sequence
+        position, so begin_index and the forced pairs move behind the prompt (generation/utils.py:943 counts the prompt the same way)."""
         cfg = self.config
         begin_index = 1 if cfg.get("forced_bos_token_id") is None else 2          # run.py:155-156 with a 1-token prompt
         forced = cfg.get("forced_decoder_ids") or []
@@ -332,6 +372,8 @@ class WhisperDecoderEngine:
             forced = timestamp_rules(cfg)[4]
         if forced:
             begin_index += forced[-1][0]                                           # run.py:157
+        begin_index += prompt_len
+        forced = [[pos + prompt_len, tok] for pos, tok in forced]
         p = _lib.GreedyParams()
         p.decoder_start_token_id = cfg["decoder_start_token_id"]
         p.eos_token_id, p.pad_token_id = cfg["eos_token_id"], cfg["pad_token_id"]
@@ -353,11 +395,11 @@ class WhisperDecoderEngine:
             p.force_eos_steps = ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32))
         return p
 
-    def _set_timestamp_rules(self, on: bool):
+    def _set_timestamp_rules(self, on: bool, prompt_len: int = 0):
         t = None
         if on:
             no_ts, tb, ts_begin, max_init, _forced = timestamp_rules(self.config)
-            t = _lib.TimestampParams(1, no_ts, tb, ts_begin, max_init)
+            t = _lib.TimestampParams(1, no_ts, tb, ts_begin + prompt_len, max_init)
         _lib.check(self.session._lib.wt_decoder_set_timestamp_rules(self.session.handle, ctypes.byref(t) if t is not None else None),
                    "wt_decoder_set_timestamp_rules")
 
@@ -386,6 +428,24 @@ class WhisperDecoderEngine:
                    "wt_decoder_set_logprobs")
         self._lp_ns = no_speech_token_id if on else None
 
+    def _set_prompt(self, rows=None):
+        t = None
+        if rows:
+            arr, _n = _i32_array([x for r in rows for x in r])
+            self._prompt_keep = arr
+            t = _lib.PromptParams(ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32)), len(rows), len(rows[0]))
+        _lib.check(self.session._lib.wt_decoder_set_prompt(self.session.handle, ctypes.byref(t) if t is not None else None), "wt_decoder_set_prompt")
+        self._prompt_len = len(rows[0]) if rows else 0
+
+    def self_kv_head(self, layer: int, head: int, which: int = 0):
+        """Debug read-back: the resident self-K (which 0) or self-V (1) rows of (layer, head), numpy float32 [B, max_target_positions, 64]."""
+        import numpy as np
+        import torch
+        out = np.empty((self._B, self.session.info.max_target_positions, 64), dtype=np.float32)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_dbg_self_kv_head(self.session.handle, layer, head, which, out.ctypes.data, ctypes.c_void_p(stream)), "wt_dbg_self_kv_head")
+        return out
+
     def _set_sampling(self, temperature: float = 0.0, seeds=()):
         t = None
         if temperature > 0:
@@ -407,7 +467,7 @@ class WhisperDecoderEngine:
         _lib.check(self.session._lib.wt_decoder_read_logprobs(self.session.handle, tok.data_ptr(), ml, total.data_ptr(),
                                                                nsp.data_ptr() if nsp is not None else None, ctypes.c_void_p(stream)),
                    "wt_decoder_read_logprobs")
-        return DecodeScores(ids, tok[:, :ids.shape[1]].clone(), total, nsp, self._p.eos_token_id)
+        return DecodeScores(ids, tok[:, :ids.shape[1]].clone(), total, nsp, self._p.eos_token_id, getattr(self, "_prompt_len", 0))
 
     def read_token_timestamps(self, cur_len: int):
         """Token-level timestamps of the decode in flight (wt_decoder_read_token_timestamps: the cross-attention DTW post-pass on the
@@ -448,8 +508,8 @@ class WhisperDecoderEngine:
     def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
               return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
               return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7,
-              return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0, seed: int = 0, seeds=None):
-        """Start a decode (wt_decoder_begin).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
+              return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0, seed: int = 0, seeds=None, prompt_ids=None):
+        """Start a decode (wt_decoder_begin).  `prompt_ids`: a decoder prompt in front of the start token (see `generate`).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
         with `seeds[b]`, or `seed + b` without a list; not with beams.  `return_logprobs` / `no_speech_token_id`: see `generate` (read with `read_logprobs`).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
         the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
         `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
@@ -471,9 +531,16 @@ class WhisperDecoderEngine:
         self._B = self._enc.shape[0]
         if force_eos_steps is not None and len(force_eos_steps) != self._B:
             raise ValueError(f"force_eos_steps needs one entry per utterance ({self._B}), got {len(force_eos_steps)}")
-        self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps)
+        prompt = None
+        if prompt_ids is not None:
+            prompt = prompt_rows(prompt_ids, self._B, i.max_target_positions)
+            _check_prompt_args(prompt, i.vocab_size, self.config["max_length"] if max_length is None else max_length, num_beams,
+                               return_token_timestamps, i.precision != 0)
+        plen = len(prompt[0]) if prompt else 0
+        self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, plen)
         self._trace = logits_trace
-        self._set_timestamp_rules(return_timestamps)
+        self._set_timestamp_rules(return_timestamps, plen)
+        self._set_prompt(prompt)
         self._set_beam_search(num_beams, length_penalty, early_stopping)
         self._set_token_timestamps(tt_heads, median_filter_width)
         self._set_logprobs(return_logprobs, no_speech_token_id)
@@ -543,8 +610,13 @@ class WhisperDecoderEngine:
                  lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, return_scores: bool = False, return_token_timestamps: bool = False, alignment_heads=None,
                  median_filter_width: int = 7, return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0,
-                 seed: int = 0, seeds=None):
+                 seed: int = 0, seeds=None, prompt_ids=None):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
+        `prompt_ids`: a decoder prompt (transformers' generate(prompt_ids=...), openai-whisper's initial_prompt / previous text): a 1-D
+        sequence shared by the batch or a 2-D [B, n] one with per-row contents of equal length, first entry <|startofprev|>, the text part
+        cut to its last max_target_positions // 2 - 1 tokens.  The prompt runs through the decoder in one pass on the device (the prefill,
+        include/whisper_trtllm_amd.h (9g)); the returned ids hold it in front of the start token, max_length counts it, and DecodeScores
+        count generated positions only.  fp32 decoder engines; not with num_beams > 1 or return_token_timestamps.
         `temperature` > 0: every token is a draw from softmax(scores / temperature) instead of the argmax (Gumbel-max over a counter-based
         generator, on the device; include/whisper_trtllm_amd.h (9f)).  Utterance b draws with `seeds[b]`, or with `seed + b`: a draw depends
         on the seed, the position and the id alone, so it is repeatable and independent of the batch.  Log-probabilities of a sampled decode
@@ -565,6 +637,14 @@ class WhisperDecoderEngine:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence score)")
         row_seeds = _check_sampling_args(temperature, seed, seeds, encoder_hidden, num_beams)
         samp = lambda i, j: {"temperature": temperature, "seeds": row_seeds[i:j]} if row_seeds else {}
+        prompt = None
+        if prompt_ids is not None:   # (begin() checks again on the single-batch path; here the rows are also needed to slice a >16-row batch)
+            info = self.session.info
+            prompt = prompt_rows(prompt_ids, encoder_hidden.shape[0], info.max_target_positions)
+            _check_prompt_args(prompt, info.vocab_size, self.config["max_length"] if max_length is None else max_length, num_beams,
+                               return_token_timestamps, info.precision != 0)
+        # the prompt rows of utterances i..j (engine batches of a larger batch slice them with the encoder rows)
+        pk = lambda i, j: {"prompt_ids": prompt if len(prompt) == 1 else prompt[i:j]} if prompt else {}
         tt = None
         if return_token_timestamps:
             _check_token_timestamp_args(self.config, self.session.info, True, alignment_heads, median_filter_width, num_beams)
@@ -597,7 +677,7 @@ class WhisperDecoderEngine:
             lp = {"return_logprobs": True, "no_speech_token_id": no_speech_token_id} if return_logprobs else {}
             parts = [self.generate(encoder_hidden[i:i + self.max_batch], max_length, force_eos_step, None, chunk,
                                    None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead,
-                                   return_timestamps, **(tt or {}), **lp, **samp(i, i + self.max_batch))
+                                   return_timestamps, **(tt or {}), **lp, **samp(i, i + self.max_batch), **pk(i, i + self.max_batch))
                      for i in range(0, encoder_hidden.shape[0], self.max_batch)]
             pad = self.config["pad_token_id"]
             cat = lambda ps, value: torch.cat([torch.nn.functional.pad(p, (0, max(q.shape[1] for q in ps) - p.shape[1]), value=value) for p in ps], dim=0)
@@ -606,17 +686,17 @@ class WhisperDecoderEngine:
                 sc = [p[-1] for p in parts]
                 scores = DecodeScores(ids, cat([x.token_logprobs for x in sc], 0.0), torch.cat([x.sum_logprob for x in sc]),
                                       torch.cat([x.no_speech_prob for x in sc]) if no_speech_token_id is not None else None,
-                                      self.config["eos_token_id"])
+                                      self.config["eos_token_id"], len(prompt[0]) if prompt else 0)
                 return (ids, cat([p[1] for p in parts], 0.0), scores) if tt else (ids, scores)
             if tt:      # every engine batch ran to its own length: its rows' times are those of that length
                 return cat([p[0] for p in parts], pad), cat([p[1] for p in parts], 0.0)
             return cat(parts, pad)
         self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, **(tt or {}),
-                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id, **samp(0, None))
+                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id, **samp(0, None), **pk(0, None))
         if chunk <= 0:
             cur, _nu = self.run(lookahead)
         else:
-            cur, done = 1, False
+            cur, done = 1 + self._prompt_len, False
             ml = self._p.max_length
             while not done and cur < ml:
                 self.steps(min(chunk, ml - cur))
@@ -637,7 +717,8 @@ class WhisperDecoderEngine:
         or the list ends; a row keeps the result of the last temperature it was decoded at.  Row i draws with `seed + i` at every
         temperature (or with `seeds[i]`, for a caller whose rows are not consecutive utterances), whichever other rows are decoded beside
         it.  `text_of(ids) -> str` gives the text whose compression ratio is taken
-        (default: the config's token decoder, or the ids in decimal).  Returns (ids int32 [B, len] padded with pad_token_id, DecodeScores,
+        (default: the config's token decoder, or the ids in decimal).  `prompt_ids` (see `generate`) goes to every try; the EOS is searched
+        behind the prompt and the compression ratio is taken of the text without it.  Returns (ids int32 [B, len] padded with pad_token_id, DecodeScores,
         temperature_used float32 [B])."""
         import torch
         from .text import compression_ratio
@@ -653,19 +734,24 @@ class WhisperDecoderEngine:
         row_seed = [int(seed) + i for i in range(B)] if seeds is None else [int(x) for x in seeds]
         if len(row_seed) < B:
             raise ValueError(f"seeds needs one entry per utterance ({B}), got {len(row_seed)}")
+        prompt = generate_kwargs.pop("prompt_ids", None)
+        if prompt is not None:
+            prompt = prompt_rows(prompt, B, self.session.info.max_target_positions)
+        plen = len(prompt[0]) if prompt else 0
         todo = list(range(B))
         rows = [None] * B                      # per original row: (ids, token_logprobs, sum_logprob, no_speech_prob, temperature)
         for t in temperatures:
             hidden = encoder_hidden if len(todo) == B else encoder_hidden[torch.as_tensor(todo, device=encoder_hidden.device)]
             ids, sc = self.generate(hidden, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
-                                    seeds=[row_seed[i] for i in todo], **generate_kwargs)
+                                    seeds=[row_seed[i] for i in todo], **generate_kwargs,
+                                    **({"prompt_ids": prompt if len(prompt) == 1 else [prompt[i] for i in todo]} if prompt else {}))
             avg = sc.avg_logprob.cpu().tolist()
             nsp = sc.no_speech_prob.cpu().tolist() if sc.no_speech_prob is not None else [None] * len(todo)
             host_ids = ids.cpu().tolist()
             again = []
             for k, i in enumerate(todo):
                 rows[i] = (ids[k], sc.token_logprobs[k], sc.sum_logprob[k], None if sc.no_speech_prob is None else sc.no_speech_prob[k], t)
-                row = host_ids[k]
+                row = host_ids[k][plen:]
                 if eos in row[1:]:
                     row = row[:row.index(eos, 1) + 1]
                 needs = False
@@ -685,7 +771,7 @@ class WhisperDecoderEngine:
         padded = lambda x, value: torch.nn.functional.pad(x, (0, width - x.shape[0]), value=value)
         ids = torch.stack([padded(r[0], pad) for r in rows])
         scores = DecodeScores(ids, torch.stack([padded(r[1], 0.0) for r in rows]), torch.stack([r[2] for r in rows]),
-                              torch.stack([r[3] for r in rows]) if rows[0][3] is not None else None, eos)
+                              torch.stack([r[3] for r in rows]) if rows[0][3] is not None else None, eos, plen)
         return ids, scores, torch.tensor([r[4] for r in rows], dtype=torch.float32, device=ids.device)
 
     def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1,
@@ -750,6 +836,7 @@ class DecodeStream:
         dec._set_beam_search(1)             # ... and so did a beam decode
         dec._set_token_timestamps(())       # ... and a decode with token-level timestamps
         dec._set_sampling(0.0)              # ... and a sampled decode
+        dec._set_prompt(None)               # ... and a decode behind a prompt
         self.pool_rows = int(pool_rows) if pool_rows else 4 * self.slots
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_decoder_stream_begin(self._h, self.slots, self.pool_rows, ctypes.byref(self._p), ctypes.c_void_p(stream)),

@@ -53,8 +53,20 @@ class WhisperTokenDecoder:
     def _bytes_to_text(self, tokens: List[str]) -> str:
         return bytearray(self.byte_decoder[c] for c in "".join(tokens)).decode("utf-8", errors=self.errors)
 
+    def _strip_prompt(self, ids: Sequence[int]) -> List[int]:
+        """The reference tokenizer's _strip_prompt (tokenization_whisper.py): ids that begin with <|startofprev|> lose everything in
+        front of <|startoftranscript|> (all of them when there is none); other ids are returned as they are."""
+        ids = [int(i) for i in ids]
+        prev, sot = self.added.get("<|startofprev|>"), self.added.get("<|startoftranscript|>")
+        if prev is None or not ids or ids[0] != prev:
+            return ids
+        return ids[ids.index(sot):] if sot in ids else []
+
     def decode(self, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
+        """skip_special_tokens also drops a leading decoder prompt (<|startofprev|> ... up to the start token), as the reference does."""
         parts, run = [], []
+        if skip_special_tokens:
+            ids = self._strip_prompt(ids)
         for i in ids:
             i = int(i)
             if (skip_special_tokens and i in self.special_ids) or i >= self.timestamp_begin:   # timestamps decode to nothing
