@@ -281,6 +281,9 @@ int wt_dbg_token_timestamp_matrix(wt_engine* dec, float* out, void* stream);
  * stands; and the bytes of the mode's device allocation (query history, head table, W, statistics, matrix, trace, output) */
 int wt_dbg_token_timestamp_postpass(wt_engine* dec, int which, void* stream);
 size_t wt_dbg_token_timestamp_bytes(const wt_engine* dec);
+/* how many step-graph captures the handle has made so far: a decode whose step configuration (csrc/host_logic.h: StepKey) repeats the
+ * previous one's captures nothing */
+int wt_dbg_step_graph_captures(const wt_engine* dec);
 /* the resident cross-K rows of one (layer, head) of the decode in flight, widened to float: HOST f32 [rows][S][64].  Synchronises. */
 int wt_dbg_cross_k_head(wt_engine* dec, int layer, int head, float* out_host, void* stream);
 /* the stages of the log-mel front-end that wt_logmel_forward does not return, as its last call on `h` with this `batch` left them:

@@ -34,7 +34,7 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_dec_embed",
                  "wt_dbg_token_timestamps_scratch_bytes", "wt_dbg_token_timestamp_matrix_kernels", "wt_dbg_token_timestamp_median",
                  "wt_dbg_token_timestamp_dtw", "wt_dbg_token_timestamp_q_hist", "wt_dbg_token_timestamp_matrix", "wt_dbg_cross_k_head",
-                 "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes",
+                 "wt_dbg_token_timestamp_postpass", "wt_dbg_token_timestamp_bytes", "wt_dbg_step_graph_captures",
                  "wt_dbg_logprob_select_scratch_bytes", "wt_dbg_logprob_select",
                  "wt_dbg_sample_select_scratch_bytes", "wt_dbg_sample_select",
                  "wt_dbg_decode_attention_state_scratch_bytes", "wt_dbg_decode_attention_state",
@@ -219,6 +219,7 @@ def load():
     lib.wt_dbg_token_timestamp_postpass.argtypes = [c_void_p, I, P]
     lib.wt_dbg_token_timestamp_bytes.argtypes = [c_void_p]
     lib.wt_dbg_token_timestamp_bytes.restype = c_size_t
+    lib.wt_dbg_step_graph_captures.argtypes = [c_void_p]
     lib.wt_dbg_logprob_select_scratch_bytes.argtypes = [I, I, I]
     lib.wt_dbg_logprob_select_scratch_bytes.restype = c_size_t
     lib.wt_dbg_logprob_select.argtypes = [I, P, P, I, P, P, POINTER(c_int32), P, I, I, I, I, I, I, I, I, POINTER(TimestampParams), I, P, P, P, P, P]

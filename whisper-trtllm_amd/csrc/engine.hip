@@ -133,8 +133,6 @@ struct wt_engine {
     int issued = 0;               // decoder steps enqueued since wt_decoder_begin
     // continuous mode (wt_decoder_stream_*): the cross caches are a POOL of rows, `B` decode slots take utterances from a device queue
     int cross_rows = 0;           // rows per layer of the resident cross caches (>= dec_cap; the pool of the continuous mode)
-    bool stream_mode = false;
-    int pool_rows = 0;            // pool rows the current stream may use (<= cross_rows)
     int* h_ids = nullptr;         // pinned, coherent [h_pool_cap][h_ml_cap]: ids of the utterance in pool row r (written by stream_finish_kernel)
     int* h_len = nullptr;         // pinned, coherent [h_pool_cap]: its final length, 0 = still waiting / decoding
     int *h_ids_dev = nullptr, *h_len_dev = nullptr;
@@ -143,59 +141,30 @@ struct wt_engine {
     int submitted = 0, finished_seen = 0, admitted_seen = 0;
     int* force_rows = nullptr;    // device [16]: per-row forced-EOS steps (bench-only variable-length workload)
     std::vector<int> h_force_rows;
-    bool force_rows_on = false;
-    // greedy session
+    // greedy session: what the wt_decoder_set_* calls asked for (resolved by the next wt_decoder_begin / wt_decoder_stream_begin) and the
+    // configuration of the decode in flight (host_logic.h; valid while `begun`)
     bool begun = false;
-    int B = 0, max_length = 0, begin_index = 0, eos = 0, pad = 0, force_eos_step = -1, nsplit_self = 1, nsplit_cross = 4, start_token = 0;
-    float* trace = nullptr;
-    // timestamp mode: the rules wt_decoder_set_timestamp_rules asked for (applied by the next wt_decoder_begin) and those of the
-    // decode in flight (enabled == 0: off)
-    wt_timestamp_params ts_req = {0, 0, 0, 0, 0}, ts_cur = {0, 0, 0, 0, 0};
-    TsPart* ts_part = nullptr;    // scratch [dec_cap][SELECT_CHUNKS] of ts_select_kernel
-    // log-probability mode: the setting wt_decoder_set_logprobs asked for (applied by the next wt_decoder_begin) and that of the decode in
-    // flight (enabled == 0: off); the partial pairs of the step and the three result buffers
-    wt_logprob_params lp_req = {0, -1}, lp_cur = {0, -1};
+    DecodeRequest req;
+    DecodeConfig cfg = {};
+    unsigned ws_gen = 1;          // bumped whenever device or pinned memory the step graphs point into moves (StepKey.workspace_gen)
+    TsPart* ts_part = nullptr;    // timestamp mode: scratch [dec_cap][SELECT_CHUNKS] of ts_select_kernel
+    // log-probability mode: the partial pairs of the step and the three result buffers
     float4* lp_part = nullptr;    // [dec_cap][SEL_PARTS_CAP]
     float *lp_side = nullptr, *lp_tok = nullptr, *lp_sum = nullptr, *lp_nsp = nullptr;   // [dec_cap][2], [dec_cap][cap_len], [dec_cap], [dec_cap]
-    // temperature sampling: the setting wt_decoder_set_sampling asked for (applied by the next wt_decoder_begin) and the temperature of the
-    // decode in flight (0: greedy; the step graph carries it).  The sampling kernels are forms of the log-probability mode's, so a sampled
-    // decode runs with that mode on.
-    float samp_req_temp = 0.f, samp_cur_temp = 0.f;
-    unsigned long long samp_req_seed = 0;
-    std::vector<unsigned long long> samp_req_seeds;   // empty: seed + row
-    bool samp_req_list = false;
+    // temperature sampling (the sampling kernels are forms of the log-probability mode's, so a sampled decode runs with that mode on)
+    std::vector<unsigned long long> h_seeds;    // host image of samp_seeds when the request gave one seed (seed + row)
     unsigned long long* samp_seeds = nullptr;   // [dec_cap]
     float* samp_sc = nullptr;                   // [dec_cap][SEL_PARTS_CAP]
     float4* samp_ts = nullptr;                  // [dec_cap][SELECT_CHUNKS]
-    // beam search: the setting wt_decoder_set_beam_search asked for (applied by the next wt_decoder_begin) and that of the decode in
-    // flight (num_beams <= 1: off).  In a beam decode B = beam_U * num_beams rows.
-    wt_beam_params beam_req = {1, 1.f, 0}, beam_cur = {1, 1.f, 0};
-    int beam_U = 0;
-    int beam_group = 0;           // > 1: the cross-attention of the beam decode in flight runs the grouped form (num_beams 2 or 4)
-    BeamParams beam_dev = {};     // device buffers of the beam state (dec_reserve; nb / U / penalty filled per decode)
-    // token-level timestamps (wt_decoder_set_token_timestamps): the setting asked for (applied by the next wt_decoder_begin) and that of the
-    // decode in flight (n_sel == 0: off); the query history the cross-attention launches fill, and the post-pass workspace
-    struct TokTs {
-        int n_sel = 0, width = 7;
-        double time_precision = 0.02;
-        int layer[TT_MAX_HEADS] = {}, head[TT_MAX_HEADS] = {};
-        bool operator==(const TokTs& o) const {
-            return n_sel == o.n_sel && width == o.width && time_precision == o.time_precision &&
-                   memcmp(layer, o.layer, sizeof layer) == 0 && memcmp(head, o.head, sizeof head) == 0;
-        }
-    } tt_req, tt_cur;
+    BeamParams beam_dev = {};     // beam search: device buffers of the beam state (dec_reserve; nb / U / penalty filled per decode)
+    // token-level timestamps: the query history the cross-attention launches fill, and the post-pass workspace
     char* tt_buf = nullptr;       // one allocation: q_hist, the per-layer head tables, W, statistics, matrix, trace, output
     size_t tt_bytes = 0;
     float *tt_qh = nullptr, *tt_W = nullptr, *tt_mean = nullptr, *tt_sdev = nullptr, *tt_matrix = nullptr, *tt_out = nullptr;
     int* tt_sel = nullptr;        // device [L][H]: selection index of (layer, head), or -1
     uint8_t* tt_trace = nullptr;
-    int tt_rows = 0, tt_steps = 0;   // q_hist / matrix dimensions of the decode in flight: rows = B, steps = max_length - 1
     std::vector<int> tt_h_sel;    // host image of tt_sel
-    // decoder prompt (wt_decoder_set_prompt): the ids asked for (applied by the next wt_decoder_begin; len 0: off), the prompt length of the
-    // decode in flight, and the prefill's workspace (allocated by the first prompt decode, grown when needed)
-    std::vector<int> prompt_req;   // [prompt_req_rows][prompt_req_len]
-    int prompt_req_rows = 0, prompt_req_len = 0, prompt_len = 0;
-    char* pf_ws = nullptr;
+    char* pf_ws = nullptr;        // decoder prompt: the prefill's workspace (allocated by the first prompt decode, grown when needed)
     size_t pf_bytes = 0;
     hipStream_t own_stream = nullptr;
     // step graphs: [0] every row attends (the only one a decode without early finishers ever replays), [1] finished rows stream no K/V,
@@ -204,8 +173,9 @@ struct wt_engine {
     hipGraph_t graph[N_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};
     hipGraphExec_t graph_exec[N_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};
     bool graph_ok[N_GRAPHS] = {false, false, false, false};
-    bool graph_valid = false, use_graph = true;
-    int nt_loads = 1;  // stream weights and K/V with non-temporal loads (set per decode in wt_decoder_begin)
+    StepKey graph_key = {};       // the key the graphs were captured under (B == 0: none yet); enqueue_steps drops them when cfg.key differs
+    int graph_captures = 0;       // step-graph captures of this handle so far (wt_dbg_step_graph_captures)
+    bool use_graph = true;
     // Session-compat shapes (set by infer_shapes)
     bool shapes_ok = false;
     int c_B = 1, c_s = 0, c_ms = 0, c_mc = 0;
@@ -563,11 +533,17 @@ static int enc_reserve(wt_engine* e, int B, hipStream_t s) {
         if (_e != hipSuccess) return fail(WT_E_HIP, "kernel launch %s failed: %s", #expr, hipGetErrorString(_e)); \
     } while (0)
 
+// LAUNCH between the two event records of `timer` (no events unless the handle is profiling)
+#define TIMED(e, timer, s, expr)                  \
+    do {                                          \
+        hipEvent_t _ta, _tb;                      \
+        timer_begin(e, timer, s, &_ta, &_tb);     \
+        LAUNCH(expr);                             \
+        timer_end(e, timer, s, _ta, _tb);         \
+    } while (0)
+
 static int timed_gemm(wt_engine* e, const GemmParams& p, hipStream_t s) {
-    hipEvent_t a, b;
-    timer_begin(e, e->t_gemm, s, &a, &b);
-    LAUNCH(launch_gemm_f32(p, s));
-    timer_end(e, e->t_gemm, s, a, b);
+    TIMED(e, e->t_gemm, s, launch_gemm_f32(p, s));
     return WT_OK;
 }
 
@@ -576,11 +552,8 @@ static int encoder_forward_f16(wt_engine* e, const float* mel, int B, float* out
     const int S = e->S, Fr = 2 * S, d = e->d, C = e->C, M = B * S;
     int rc;
     auto hgemm = [&](const GemmParams& q, bool out_half) {
-        hipEvent_t a, b;
-        timer_begin(e, e->t_gemm, s, &a, &b);
-        hipError_t le = launch_gemm_f16(q, out_half, s);
-        timer_end(e, e->t_gemm, s, a, b);
-        return le == hipSuccess ? WT_OK : fail(WT_E_HIP, "fp16 GEMM launch failed: %s", hipGetErrorString(le));
+        TIMED(e, e->t_gemm, s, launch_gemm_f16(q, out_half, s));
+        return (int)WT_OK;
     };
     LAUNCH(launch_mel_transpose_h(mel, e->melT_h, B, C, Fr, s));
     {
@@ -604,12 +577,7 @@ static int encoder_forward_f16(wt_engine* e, const float* mel, int B, float* out
         const EncLayerW& l = e->enc_layers[i];
         LAUNCH(launch_layernorm_h(e->hbuf, l.ln1_w, l.ln1_b, e->x_h, M, d, s));
         if ((rc = dense(e->x_h, d, l.qkv_w, l.qkv_b, 3 * d, e->qkv, 0, nullptr, true))) return rc;   // q|k|v as fp16
-        {
-            hipEvent_t a, b;
-            timer_begin(e, e->t_enc_attn, s, &a, &b);
-            LAUNCH(launch_encoder_attention_f16(e->qkv, e->ctx_h, B, S, e->H, s));                      // fp16 in/out, fp32 softmax
-            timer_end(e, e->t_enc_attn, s, a, b);
-        }
+        TIMED(e, e->t_enc_attn, s, launch_encoder_attention_f16(e->qkv, e->ctx_h, B, S, e->H, s));   // fp16 in/out, fp32 softmax
         if ((rc = dense(e->ctx_h, d, l.o_w, l.o_b, d, e->hbuf, 0, e->hbuf, false))) return rc;
         LAUNCH(launch_layernorm_h(e->hbuf, l.ln2_w, l.ln2_b, e->x_h, M, d, s));
         if ((rc = dense(e->x_h, d, l.fc1_w, l.fc1_b, e->F, e->ffn_h, 1, nullptr, true))) return rc;
@@ -639,12 +607,7 @@ extern "C" int wt_encoder_forward(wt_engine* e, const float* mel, int B, float* 
         if (gemm_x3_usable(c1g) && gemm_x3_usable(c2g)) {
             convs_x3 = true;
             LAUNCH(launch_mel_transpose_split(mel, e->melT3, e->melT3_plane, B, C, Fr, s));
-            for (const GemmParams* q : {&c1g, &c2g}) {
-                hipEvent_t a, b;
-                timer_begin(e, e->t_gemm, s, &a, &b);
-                LAUNCH(launch_gemm_x3(*q, s));
-                timer_end(e, e->t_gemm, s, a, b);
-            }
+            for (const GemmParams* q : {&c1g, &c2g}) TIMED(e, e->t_gemm, s, launch_gemm_x3(*q, s));
         }
     }
     if (!convs_x3) {
@@ -673,11 +636,8 @@ extern "C" int wt_encoder_forward(wt_engine* e, const float* mel, int B, float* 
         q.A = (const float*)A3; q.lda = K; q.a_rows_per_batch = M; q.a_plane = (long long)M * K; q.W = (const float*)W3; q.w_plane = (long long)N * K;
         q.bias = bias; q.M = M; q.N = N; q.K = K; q.act = act; q.C = (float*)Cout; q.ldc = N; q.c_rows_per_batch = M; q.resid = resid;
         q.out_split = out_split ? 1 : 0; q.c_plane = (long long)M * N;
-        hipEvent_t a, b;
-        timer_begin(e, e->t_gemm, s, &a, &b);
-        LAUNCH(launch_gemm_x3(q, s));
-        timer_end(e, e->t_gemm, s, a, b);
-        return WT_OK;
+        TIMED(e, e->t_gemm, s, launch_gemm_x3(q, s));
+        return (int)WT_OK;
     };
     if (e->use_x3) {
         // fp32 products formed from six bf16 MFMAs of exactly split operands (wt_common.h: launch_gemm_x3): every producer of a GEMM's
@@ -688,13 +648,8 @@ extern "C" int wt_encoder_forward(wt_engine* e, const float* mel, int B, float* 
             LAUNCH(launch_layernorm_split(e->hbuf, l.ln1_w, l.ln1_b, e->xs3, pl_d, M, d, s));
             static const bool attn_x3 = !(tuning_env("WT_ATTN_X3") && atoi(tuning_env("WT_ATTN_X3")) == 0);   // A/B switch: fp32-MFMA attention
             if ((rc = dense3(e->xs3, d, l.qkv_w3, l.qkv_b, 3 * d, attn_x3 ? e->qkv3 : (void*)e->qkv, 0, nullptr, attn_x3))) return rc;
-            {
-                hipEvent_t a, b;
-                timer_begin(e, e->t_enc_attn, s, &a, &b);
-                if (attn_x3) LAUNCH(launch_encoder_attention_x3(e->qkv3, (size_t)M * 3 * d, e->ctx3, pl_d, B, S, e->H, s));
-                else LAUNCH(launch_encoder_attention(e->qkv, nullptr, B, S, e->H, s, e->ctx3, pl_d));
-                timer_end(e, e->t_enc_attn, s, a, b);
-            }
+            if (attn_x3) TIMED(e, e->t_enc_attn, s, launch_encoder_attention_x3(e->qkv3, (size_t)M * 3 * d, e->ctx3, pl_d, B, S, e->H, s));
+            else TIMED(e, e->t_enc_attn, s, launch_encoder_attention(e->qkv, nullptr, B, S, e->H, s, e->ctx3, pl_d));
             if ((rc = dense3(e->ctx3, d, l.o_w3, l.o_b, d, e->hbuf, 0, e->hbuf, false))) return rc;
             LAUNCH(launch_layernorm_split(e->hbuf, l.ln2_w, l.ln2_b, e->xs3, pl_d, M, d, s));
             if ((rc = dense3(e->xs3, d, l.fc1_w3, l.fc1_b, e->F, e->ffn3, 1, nullptr, true))) return rc;
@@ -707,12 +662,7 @@ extern "C" int wt_encoder_forward(wt_engine* e, const float* mel, int B, float* 
         const EncLayerW& l = e->enc_layers[i];
         LAUNCH(launch_layernorm(e->hbuf, l.ln1_w, l.ln1_b, e->xbuf, M, d, s));
         if ((rc = dense(e->xbuf, d, l.qkv_w, l.qkv_b, 3 * d, e->qkv, 0, nullptr))) return rc;
-        {
-            hipEvent_t a, b;
-            timer_begin(e, e->t_enc_attn, s, &a, &b);
-            LAUNCH(launch_encoder_attention(e->qkv, e->ctx, B, S, e->H, s));
-            timer_end(e, e->t_enc_attn, s, a, b);
-        }
+        TIMED(e, e->t_enc_attn, s, launch_encoder_attention(e->qkv, e->ctx, B, S, e->H, s));
         if ((rc = dense(e->ctx, d, l.o_w, l.o_b, d, e->hbuf, 0, e->hbuf))) return rc;
         LAUNCH(launch_layernorm(e->hbuf, l.ln2_w, l.ln2_b, e->xbuf, M, d, s));
         if ((rc = dense(e->xbuf, d, l.fc1_w, l.fc1_b, e->F, e->ffn, 1, nullptr))) return rc;
@@ -729,7 +679,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     if (max_length < e->dec_maxlen_cap) max_length = e->dec_maxlen_cap;
     if (pool_rows < e->cross_rows) pool_rows = e->cross_rows;
     if (e->dec_ws) { hipFree(e->dec_ws); e->dec_ws = nullptr; e->dec_cap = 0; e->cross_rows = 0; }
-    e->graph_valid = false;
+    e->ws_gen += 1;
     e->tables_valid = false;
     const int cap_len = max_length > e->T ? max_length : e->T;
     const int cross_rows = pool_rows > B ? pool_rows : B, enc_rows = B > MAX_ROWS ? B : MAX_ROWS;
@@ -793,17 +743,6 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     return WT_OK;
 }
 
-static int pick_splits(int B, int H, int len) {
-    // Key splits of the cross-attention launch.  Two splits are merged for free by the consuming GEMV (deferred merge), more
-    // are merged by the attention kernel's last-arriving block, which costs ~2 us: measured on medium.en, ms per step at
-    // B = 1: 16 splits 1.25, 8: 1.12, 4: 1.09, 2: 1.14;  B = 2: 8: 1.16, 4: 1.12, 2: 1.15;  B = 4: 4: 1.27, 2: 1.26;
-    // B = 8: 2: 1.47, 3: 1.76, 4: 1.80.  So: 4 while (utterance, head) pairs are scarce (<= 64), else 2, none from 256 pairs up.
-    int n = (256 + B * H - 1) / (B * H);
-    n = n >= 4 ? 4 : n >= 2 ? 2 : 1;   // (tiny.en B = 8, 48 pairs: 4 splits 0.218, 2 splits 0.225; small.en B = 8, 96 pairs: 2 splits 0.693, 4: 0.706)
-    while (n > 1 && len / n < 48) n >>= 1;
-    return n;
-}
-
 // one decoder step over the resident (or caller-provided) caches; every step-dependent quantity comes from *st
 struct StepIO {
     const int* ids; int ids_ld;            // token fed to row b = ids[b*ids_ld + st->cur_len-1]
@@ -820,6 +759,7 @@ struct StepIO {
     int kv_esz;                            // bytes per cache element: 4 (fp32; always on the Session path), 2 (resident caches of an fp16 engine)
     float* logits;                         // [B][V]
     int B, nsplit_self, nsplit_cross;
+    int nt;                                // stream weights and K/V with non-temporal loads (StepKey.nt_loads)
     const int* alive;                      // skip-finished-rows graph of the fast path: per-row "unfinished" flags (DecAttnParams.alive)
     bool embed;                            // launch the input-embedding kernel (the fast path gets it from greedy_finish)
     // greedy fast path: masked argmax fused into the vocabulary GEMV (logits == nullptr: they never reach HBM unless traced)
@@ -853,9 +793,9 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
     memset(&a, 0, sizeof a);
     switch (part) {
     case LP_QKV:  // self attention (model.py:273-281, 283-304): LN -> q|k|v, append k/v row in place
-        k = qkv_append_skinny_params(h, l.ln1_w, l.ln1_b, l.qkv_w, l.qkv_b, e->dq, sk, sv, e->st, B, d, io.self_cap, e->nt_loads, wh, kvh);
+        k = qkv_append_skinny_params(h, l.ln1_w, l.ln1_b, l.qkv_w, l.qkv_b, e->dq, sk, sv, e->st, B, d, io.self_cap, io.nt, wh, kvh);
         if (hoist) {   // + uh = fold_wh . h + fold_c on the raw row, in the same launch
-            k2 = qfold_resid_skinny_params(h, l.fold_wh, l.fold_c, e->duh, e->st, B, d, e->nt_loads, wh);
+            k2 = qfold_resid_skinny_params(h, l.fold_wh, l.fold_c, e->duh, e->st, B, d, io.nt, wh);
             LAUNCH(launch_skinny_qkv_hoist(k, k2, s));
         } else {
             LAUNCH(launch_skinny(k, s));
@@ -863,7 +803,7 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
         break;
     case LP_SELF_ATTN:
         a.q = e->dq; a.kcache = sk; a.vcache = sv; a.part = e->part; a.cnt = e->att_cnt; a.out = e->datt; a.st = e->st; a.B = B; a.H = H; a.s_cap = io.self_cap;
-        a.n_split = io.nsplit_self; a.fixed_len = 0; a.nt = e->nt_loads; a.kv_half = kvh; a.alive = io.alive;
+        a.n_split = io.nsplit_self; a.fixed_len = 0; a.nt = io.nt; a.kv_half = kvh; a.alive = io.alive;
         a.anc = io.anc; a.anc_ld = io.anc_ld;
         a.defer_merge = defer && io.nsplit_self == 2;   // both halves of the pair launch below merge the two partials while staging
         LAUNCH(launch_dec_attn(a, s));
@@ -873,13 +813,13 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
         // u = s.Wq.diag(gamma2).(h + Wo.a + bo) = fold_w.[a ; h] + fold_c; LayerNorm statistics of h1 are applied
         // by the cross-attention kernel (model.py:261-272 semantics, one dependent launch fewer per layer)
         k.X = e->datt; k.xmode = XMODE_PLAIN; k.W = l.o_w; k.bias = l.o_b; k.resid = h;
-        k.Y = h1; k.st = e->st; k.B = B; k.N = d; k.K = d; k.q_scale = 1.f; k.w_nt = e->nt_loads; k.w_half = wh;
+        k.Y = h1; k.st = e->st; k.B = B; k.N = d; k.K = d; k.q_scale = 1.f; k.w_nt = io.nt; k.w_half = wh;
         if (hoist) {   // u = fold_wa . a + uh: both halves of the launch read only `a`, staged (and merged) once per workgroup
             k2 = qfold_ctx_skinny_params(e->datt, defer && io.nsplit_self == 2 ? e->part : nullptr, l.fold_wa, e->duh, e->dq, e->st, B, d,
-                                         e->nt_loads, wh);
+                                         io.nt, wh);
         } else {
             k2.X = e->datt; k2.X2 = h; k2.xmode = XMODE_PLAIN; k2.x_direct = 1; k2.W = l.fold_w; k2.bias = l.fold_c;
-            k2.Y = e->dq; k2.st = e->st; k2.B = B; k2.N = d; k2.K = 2 * d; k2.q_scale = 1.f; k2.w_nt = e->nt_loads; k2.w_half = wh;
+            k2.Y = e->dq; k2.st = e->st; k2.B = B; k2.N = d; k2.K = 2 * d; k2.q_scale = 1.f; k2.w_nt = io.nt; k2.w_half = wh;
         }
         if (defer && io.nsplit_self == 2) {   // the self-attention context `a` arrives as two split partials per (utterance, head)
             k.parts = e->part; k.parts_nsplit = 2; k.parts_H = H;
@@ -889,32 +829,29 @@ static int enqueue_layer_part(wt_engine* e, const StepIO& io, int i, float* h, f
         break;
     case LP_CROSS_ATTN: {  // cross attention over the encoder memory: K/V already resident
         a.q = e->dq; a.kcache = ck; a.vcache = cv; a.part = e->part; a.cnt = e->att_cnt; a.out = e->datt; a.st = e->st; a.B = B; a.H = H; a.s_cap = e->S;
-        a.n_split = io.nsplit_cross; a.fixed_len = e->S; a.nt = e->nt_loads; a.ln_h = h1; a.ln_r = l.fold_r; a.ln_t = l.fold_t; a.kv_half = kvh;
+        a.n_split = io.nsplit_cross; a.fixed_len = e->S; a.nt = io.nt; a.ln_h = h1; a.ln_r = l.fold_r; a.ln_t = l.fold_t; a.kv_half = kvh;
         a.alive = io.alive; a.slot_row = io.slot_row;
         if (io.group > 1) { a.group = io.group; a.slot_row = nullptr; }
         if (io.qh) { a.qh = io.qh; a.qh_sel = io.qh_sel + (size_t)i * H; a.qh_rows = io.qh_rows; a.qh_steps = io.qh_steps; }
         a.defer_merge = defer && io.nsplit_cross == 2;  // the out-projection below merges the two split partials while staging them
                                                         // (more splits, i.e. batch < 8: the attention kernel merges its own, by ticket)
-        hipEvent_t ta, tb;
-        timer_begin(e, e->t_cross, s, &ta, &tb);
-        LAUNCH(launch_dec_attn(a, s));
-        timer_end(e, e->t_cross, s, ta, tb);
+        TIMED(e, e->t_cross, s, launch_dec_attn(a, s));
         break;
     }
     case LP_CROSS_OUT:
         k.X = e->datt; k.xmode = XMODE_PLAIN; k.W = l.co_w; k.bias = l.co_b; k.resid = h1;
-        k.Y = h1; k.st = e->st; k.B = B; k.N = d; k.K = d; k.q_scale = 1.f; k.w_nt = e->nt_loads; k.w_half = wh;
+        k.Y = h1; k.st = e->st; k.B = B; k.N = d; k.K = d; k.q_scale = 1.f; k.w_nt = io.nt; k.w_half = wh;
         if (defer && io.nsplit_cross == 2) { k.parts = e->part; k.parts_nsplit = io.nsplit_cross; k.parts_H = H; }
         LAUNCH(launch_skinny(k, s));
         break;
     case LP_FC1:  // FFN (model.py:363-367)
         k.X = h1; k.ln_w = l.ln3_w; k.ln_b = l.ln3_b; k.xmode = XMODE_LAYERNORM; k.W = l.fc1_w; k.bias = l.fc1_b;
-        k.Y = e->dffn; k.st = e->st; k.B = B; k.N = e->F; k.K = d; k.act = 1; k.q_scale = 1.f; k.w_nt = e->nt_loads; k.w_half = wh;
+        k.Y = e->dffn; k.st = e->st; k.B = B; k.N = e->F; k.K = d; k.act = 1; k.q_scale = 1.f; k.w_nt = io.nt; k.w_half = wh;
         LAUNCH(launch_skinny(k, s));
         break;
     case LP_FC2:
         k.X = e->dffn; k.xmode = XMODE_PLAIN; k.W = l.fc2_w; k.bias = l.fc2_b; k.resid = h1; k.Y = h1; k.st = e->st;
-        k.B = B; k.N = d; k.K = e->F; k.q_scale = 1.f; k.w_nt = e->nt_loads; k.w_half = wh;
+        k.B = B; k.N = d; k.K = e->F; k.q_scale = 1.f; k.w_nt = io.nt; k.w_half = wh;
         LAUNCH(launch_skinny(k, s));
         break;
     default:
@@ -938,18 +875,13 @@ static int enqueue_step(wt_engine* e, const StepIO& io, hipStream_t s) {
         std::swap(h, h1);
     }
     // final LN + vocabulary projection (model.py:455-457; logits are the engine's 'hidden_states' output)
-    k = vocab_skinny_params(h, e->dec_ln_w, e->dec_ln_b, e->proj_w, io.logits, e->st, B, e->V, d, e->nt_loads, e->w_half);
+    k = vocab_skinny_params(h, e->dec_ln_w, e->dec_ln_b, e->proj_w, io.logits, e->st, B, e->V, d, io.nt, e->w_half);
     if (io.argmax) {  // Suppress -> SuppressAtBegin -> argmax in the epilogue (Force / pad / EOS rules: greedy_finish_kernel)
         const int grid = vocab_skinny_fuse_argmax(k, *io.argmax);
         if (grid < 1 || grid > SEL_PARTS_CAP) return fail(WT_E_UNSUPPORTED, "vocabulary GEMV plan has %d workgroups (cap %d)", grid, SEL_PARTS_CAP);
         *io.argmax_parts = grid;
     }
-    {
-        hipEvent_t ta, tb;
-        timer_begin(e, e->t_skinny, s, &ta, &tb);
-        LAUNCH(launch_skinny(k, s));
-        timer_end(e, e->t_skinny, s, ta, tb);
-    }
+    TIMED(e, e->t_skinny, s, launch_skinny(k, s));
     return WT_OK;
 }
 
@@ -977,16 +909,10 @@ static int cross_kv_project(wt_engine* e, const float* enc_hidden, int B, int ro
         const size_t layer = (size_t)i * layer_rows * row_bytes;
         GemmParams g = cross_kv_gemm_params(A, e->S, l.ckv_w, l.ckv_b, (char*)ck + layer, (char*)cv + layer, kv_esz, B, rows, e->H, e->S, seq_off, row0);
         if (e->w_half) {
-            hipEvent_t ta, tb;
-            timer_begin(e, e->t_gemm, s, &ta, &tb);
-            LAUNCH(launch_gemm_f16(g, kv_esz == 2, s));
-            timer_end(e, e->t_gemm, s, ta, tb);
+            TIMED(e, e->t_gemm, s, launch_gemm_f16(g, kv_esz == 2, s));
         } else if (x3) {
             cross_kv_x3(g, e->enc3, enc_plane, l.ckv_w3);
-            hipEvent_t ta, tb;
-            timer_begin(e, e->t_gemm, s, &ta, &tb);
-            LAUNCH(launch_gemm_x3(g, s));
-            timer_end(e, e->t_gemm, s, ta, tb);
+            TIMED(e, e->t_gemm, s, launch_gemm_x3(g, s));
         } else {
             int rc = timed_gemm(e, g, s);
             if (rc) return rc;
@@ -997,9 +923,8 @@ static int cross_kv_project(wt_engine* e, const float* enc_hidden, int B, int ro
 
 // token-level timestamps: (re)allocate the query history and the post-pass workspace for `B` rows of `max_length - 1` steps and upload the
 // per-layer head tables.  The buffer only grows; its layout is recomputed per decode.
-static int tt_reserve(wt_engine* e, const wt_engine::TokTs& tt, int B, int max_length, hipStream_t s) {
-    const int n = tt.n_sel, steps = max_length - 1, S = e->S, ld = tt_trace_ld(S);
-    if (steps > TT_MAX_TOKENS) return fail(WT_E_UNSUPPORTED, "token timestamps: %d steps > %d", steps, TT_MAX_TOKENS);
+static int tt_reserve(wt_engine* e, const StepKey& k, hipStream_t s) {
+    const int n = k.tt.n_sel, B = k.tt_rows, steps = k.tt_steps, max_length = k.max_length, S = e->S, ld = tt_trace_ld(S);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     // the head table comes first: its address does not depend on the decode's dimensions
@@ -1012,19 +937,14 @@ static int tt_reserve(wt_engine* e, const wt_engine::TokTs& tt, int B, int max_l
         hipError_t he = hipMalloc((void**)&e->tt_buf, off);
         if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for the token-timestamp workspace failed: %s", off, hipGetErrorString(he));
         e->tt_bytes = off;
-        e->graph_valid = false;
-        e->tt_h_sel.clear();
+        e->ws_gen += 1;
+        e->tt_h_sel.clear();   // the table moved: whatever lies there is not the table, upload it again
     }
     char* b = e->tt_buf;
-    float* qh = (float*)(b + o_qh);
-    int* sel = (int*)(b + o_sel);
-    if (qh != e->tt_qh || sel != e->tt_sel || e->tt_rows != B || e->tt_steps != steps) e->graph_valid = false;
-    if (sel != e->tt_sel) e->tt_h_sel.clear();   // the table moved: whatever lies there is not the table, upload it again
-    e->tt_qh = qh; e->tt_sel = sel; e->tt_W = (float*)(b + o_W); e->tt_mean = (float*)(b + o_mean); e->tt_sdev = (float*)(b + o_sdev);
+    e->tt_qh = (float*)(b + o_qh); e->tt_sel = (int*)(b + o_sel); e->tt_W = (float*)(b + o_W); e->tt_mean = (float*)(b + o_mean); e->tt_sdev = (float*)(b + o_sdev);
     e->tt_matrix = (float*)(b + o_mat); e->tt_trace = (uint8_t*)(b + o_tr); e->tt_out = (float*)(b + o_out);
-    e->tt_rows = B; e->tt_steps = steps;
     std::vector<int> tab((size_t)e->L * e->H, -1);
-    for (int i = 0; i < n; ++i) tab[(size_t)tt.layer[i] * e->H + tt.head[i]] = i;
+    for (int i = 0; i < n; ++i) tab[(size_t)k.tt.layer[i] * e->H + k.tt.head[i]] = i;
     if (tab != e->tt_h_sel) {
         e->tt_h_sel.swap(tab);
         HIPCHK(hipMemcpyAsync(e->tt_sel, e->tt_h_sel.data(), e->tt_h_sel.size() * 4, hipMemcpyHostToDevice, s));
@@ -1035,40 +955,58 @@ static int tt_reserve(wt_engine* e, const wt_engine::TokTs& tt, int B, int max_l
     return WT_OK;
 }
 
-// Everything wt_decoder_begin and wt_decoder_stream_begin share: argument checks, workspace, token-rule tables, cache policy and key
-// splits of the step graph.  `B` = rows of the batch / decode slots of the stream; `pool_rows` = cross-cache rows (0: B).
-static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool_rows, bool stream_mode, hipStream_t s, const char* who,
-                        const wt_beam_params beam = wt_beam_params{1, 1.f, 0}) {
-    if (B > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "%s: batch %d > %d per call; shard the batch", who, B, MAX_ROWS);
-    if (p->max_length < 2 || p->max_length > e->T) return fail(WT_E_INVALID, "max_length %d outside [2, max_target_positions=%d]", p->max_length, e->T);
-    auto tok_ok = [&](int t) { return t >= 0 && t < e->V; };
-    if (!tok_ok(p->decoder_start_token_id) || !tok_ok(p->eos_token_id) || !tok_ok(p->pad_token_id))
-        return fail(WT_E_INVALID, "start/eos/pad token id outside the vocabulary");
-    int rc = dec_reserve(e, B, p->max_length, s, pool_rows);
+static EngineDims engine_dims(const wt_engine* e) {
+    EngineDims dims;
+    dims.kind = e->kind; dims.precision = e->precision; dims.d = e->d; dims.H = e->H; dims.L = e->L; dims.F = e->F;
+    dims.C = e->C; dims.S = e->S; dims.T = e->T; dims.V = e->V;
+    return dims;
+}
+
+// the pinned report area of the continuous mode: ids and final lengths per pool row
+static int stream_reserve(wt_engine* e, int pool_rows, hipStream_t s) {
+    if (pool_rows <= e->h_pool_cap && e->dec_maxlen_cap <= e->h_ml_cap) return WT_OK;
+    HIPCHK(hipStreamSynchronize(s));   // no step of an earlier stream may still write the old area
+    const int rows = pool_rows > e->h_pool_cap ? pool_rows : e->h_pool_cap;
+    if (e->h_ids) { hipHostFree(e->h_ids); e->h_ids = nullptr; }
+    if (e->h_len) { hipHostFree(e->h_len); e->h_len = nullptr; }
+    e->h_pool_cap = 0;
+    HIPCHK(hipHostMalloc((void**)&e->h_ids, (size_t)rows * e->dec_maxlen_cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostMalloc((void**)&e->h_len, (size_t)rows * 4, hipHostMallocMapped | hipHostMallocCoherent));
+    HIPCHK(hipHostGetDevicePointer((void**)&e->h_ids_dev, e->h_ids, 0));
+    HIPCHK(hipHostGetDevicePointer((void**)&e->h_len_dev, e->h_len, 0));
+    e->h_pool_cap = rows;
+    e->h_ml_cap = e->dec_maxlen_cap;
+    e->ws_gen += 1;   // the step graph carries these addresses
+    return WT_OK;
+}
+
+// Everything wt_decoder_begin and wt_decoder_stream_begin share: the decode configuration (resolve_decode_config: every check, cache
+// policy and key splits), workspace and token-rule tables.  `rows` = utterances of the batch / decode slots of the stream; `pool_rows` =
+// cross-cache rows of the stream.  e->cfg changes only when all of it succeeded.
+static int decode_setup(wt_engine* e, int rows, const wt_greedy_params* p, int pool_rows, bool stream, hipStream_t s) {
+    DecodeFacts f;
+    f.w_half = e->w_half; f.kv_esz = e->kv_esz;
+    f.no_defer_merge = tuning_env("WT_NO_DEFER_MERGE") != nullptr;
+    if (tuning_env("WT_NSPLIT_SELF")) f.nsplit_self = atoi(tuning_env("WT_NSPLIT_SELF"));
+    if (tuning_env("WT_NSPLIT_CROSS")) { f.nsplit_cross_set = true; f.nsplit_cross = atoi(tuning_env("WT_NSPLIT_CROSS")); }
+    f.beam_cross_grouped = tuning_env("WT_BEAM_CROSS") && !strcmp(tuning_env("WT_BEAM_CROSS"), "grouped");
+    DecodeConfig cfg;
+    char msg[400] = "";
+    int rc = resolve_decode_config(engine_dims(e), f, e->req, p, rows, pool_rows, stream, &cfg, msg, sizeof msg);   // host_logic.cpp
+    if (rc) return fail(rc, "%s", msg);
+    const StepKey& k = cfg.key;
+    rc = dec_reserve(e, k.B, k.max_length, s, cfg.pool_rows);
     if (rc) return rc;
-    // token rules -> device tables (SuppressTokens / SuppressTokensAtBegin / ForceTokens).  The host images live in the engine:
-    // when the rules are the ones of the previous decode (the usual case: one rule set per checkpoint) nothing is uploaded and
-    // the call stays asynchronous; only a CHANGED rule set is uploaded, followed by one stream synchronisation.
+    // token rules -> device tables (SuppressTokens / SuppressTokensAtBegin / ForceTokens; the ids were checked by the resolver).  The
+    // host images live in the engine: when the rules are the ones of the previous decode (the usual case: one rule set per checkpoint)
+    // nothing is uploaded and the call stays asynchronous; only a CHANGED rule set is uploaded, followed by one stream synchronisation.
     std::vector<uint8_t> mask(e->V, 0);
-    for (int i = 0; i < p->n_suppress_tokens; ++i) {
-        if (!tok_ok(p->suppress_tokens[i])) return fail(WT_E_INVALID, "suppress token %d outside the vocabulary", p->suppress_tokens[i]);
-        mask[p->suppress_tokens[i]] |= 1;
-    }
-    for (int i = 0; i < p->n_begin_suppress_tokens; ++i) {
-        if (!tok_ok(p->begin_suppress_tokens[i])) return fail(WT_E_INVALID, "begin-suppress token %d outside the vocabulary", p->begin_suppress_tokens[i]);
-        mask[p->begin_suppress_tokens[i]] |= 2;
-    }
-    const wt_timestamp_params ts = stream_mode || !e->ts_req.enabled ? wt_timestamp_params{0, 0, 0, 0, 0} : e->ts_req;
+    for (int i = 0; i < p->n_suppress_tokens; ++i) mask[p->suppress_tokens[i]] |= 1;
+    for (int i = 0; i < p->n_begin_suppress_tokens; ++i) mask[p->begin_suppress_tokens[i]] |= 2;
     std::vector<int> forced(e->dec_maxlen_cap + 1, -1);
     for (int i = 0; i < p->n_forced; ++i) {
-        const int idx = p->forced_decoder_ids[2 * i], tok = p->forced_decoder_ids[2 * i + 1];
-        if (!tok_ok(tok)) return fail(WT_E_INVALID, "forced token %d outside the vocabulary", tok);
-        if (ts.enabled && (tok == ts.no_timestamps_token_id || idx >= ts.begin_index - 1))   // Force and Timestamp must not fight
-            return fail(WT_E_INVALID, "timestamp mode: forced token %d at %d (no <|notimestamps|>, no forced position >= begin_index - 1 = %d)",
-                        tok, idx, ts.begin_index - 1);
-        if (beam.num_beams > 1 && tok == p->eos_token_id)
-            return fail(WT_E_INVALID, "beam search: forced token %d is the EOS token (no beam could continue)", tok);
-        if (idx >= 0 && idx <= e->dec_maxlen_cap) forced[idx] = tok;
+        const int idx = p->forced_decoder_ids[2 * i];
+        if (idx >= 0 && idx <= e->dec_maxlen_cap) forced[idx] = p->forced_decoder_ids[2 * i + 1];
     }
     if (!e->tables_valid || mask != e->h_mask || forced != e->h_forced) {
         e->tables_valid = false;   // a failed upload below must not leave "valid" tables whose host images already hold the new rules
@@ -1079,84 +1017,26 @@ static int decode_setup(wt_engine* e, int B, const wt_greedy_params* p, int pool
         HIPCHK(hipStreamSynchronize(s));  // pageable sources: make sure the copies have left the host images before they can change
         e->tables_valid = true;
     }
-    {   // bench-only per-row transcript lengths: uploaded (with one synchronisation) only when they change
-        std::vector<int> rows;
-        if (p->force_eos_steps && !stream_mode) rows.assign(p->force_eos_steps, p->force_eos_steps + B);
-        const bool on = !rows.empty();
-        if (on && rows != e->h_force_rows) {
-            e->h_force_rows.swap(rows);
-            HIPCHK(hipMemcpyAsync(e->force_rows, e->h_force_rows.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+    if (k.force_rows_on) {   // bench-only per-row transcript lengths: uploaded (with one synchronisation) only when they change
+        std::vector<int> lens(p->force_eos_steps, p->force_eos_steps + k.B);
+        if (lens != e->h_force_rows) {
+            e->h_force_rows.swap(lens);
+            HIPCHK(hipMemcpyAsync(e->force_rows, e->h_force_rows.data(), (size_t)k.B * 4, hipMemcpyHostToDevice, s));
             HIPCHK(hipStreamSynchronize(s));
         }
-        if (on != e->force_rows_on) e->graph_valid = false;
-        e->force_rows_on = on;
     }
-    // token-level timestamps: workspace and head tables of this decode (a changed setting re-captures the step graphs)
-    const wt_engine::TokTs tt = stream_mode || beam.num_beams > 1 ? wt_engine::TokTs{} : e->tt_req;
-    if (tt.n_sel > 0) {
-        rc = tt_reserve(e, tt, B, p->max_length, s);
-        if (rc) return rc;
-    }
-    if (!(tt == e->tt_cur)) e->graph_valid = false;
-    e->tt_cur = tt;
-    const bool same = e->begun && e->B == B && e->max_length == p->max_length && e->trace == p->logits_trace &&
-                      e->begin_index == p->begin_index && e->eos == p->eos_token_id && e->pad == p->pad_token_id &&
-                      e->force_eos_step == p->force_eos_step && e->start_token == p->decoder_start_token_id &&
-                      memcmp(&e->ts_cur, &ts, sizeof ts) == 0 && memcmp(&e->beam_cur, &beam, sizeof beam) == 0;
-    if (!same) e->graph_valid = false;
-    e->ts_cur = ts;
-    e->beam_cur = beam;
-    e->B = B; e->max_length = p->max_length; e->begin_index = p->begin_index; e->eos = p->eos_token_id;
-    e->pad = p->pad_token_id; e->force_eos_step = p->force_eos_step; e->trace = p->logits_trace; e->start_token = p->decoder_start_token_id;
-    // measured (tools/microbench.py, medium.en B=8): self attention is fastest unsplit at every length <= 448;
-    // cross attention (1500 keys) with ~one block per CU
-    {   // Everything a step touches is read exactly once per step: stream it non-temporally -- unless one whole step (weights + this
-        // batch's K/V) fits the 256 MB Infinity Cache, where default-policy loads let step t+1 hit what step t brought in.
-        // Measured ms per step, non-temporal vs default: tiny.en B=1 (136 MB) 0.171 vs 0.160; tiny.en B=8 (300 MB) 0.224 vs 0.221;
-        // base.en B=8 0.324 vs 0.340; small.en B=8 0.688 vs 0.711; medium.en B=8 1.61 vs 1.66.
-        const double p_step = (double)e->L * (6.0 * e->d * e->d + 2.0 * e->d * e->F) + (double)e->V * e->d;
-        const double step_bytes = (e->w_half ? 2.0 : 4.0) * p_step + (double)B * 2.0 * e->L * e->H * ((double)e->S + p->max_length) * HEAD_DIM * e->kv_esz;
-        const int nt = step_bytes > 160e6;
-        if (nt != e->nt_loads) e->graph_valid = false;
-        e->nt_loads = nt;
-    }
-    // self attention: unsplit.  Two key splits with the merge deferred into BOTH halves of the pair launch (WT_NSPLIT_SELF=2) are
-    // implemented and tested, and measured a wash at medium.en batch 8: self-attention 9.0 -> 7.6 us at 447 keys, the pair launch
-    // 8.2 -> 9.7 us (its blocks stage and merge two partial sets), 1.659 vs 1.649 ms per step in one A/B on one box.
-    {
-        const bool can_defer = tuning_env("WT_NO_DEFER_MERGE") == nullptr && e->d <= 1024;
-        const int want = tuning_env("WT_NSPLIT_SELF") ? atoi(tuning_env("WT_NSPLIT_SELF")) : 1;
-        const int ns = (want == 2 && can_defer) ? 2 : 1;
-        if (ns != e->nsplit_self) e->graph_valid = false;
-        e->nsplit_self = ns;
-    }
-    {   // beam search: the cross-attention form.  The shared cache rows are read once per beam through slot_row (B blocks per head).  The
-        // grouped form (one block per (utterance, head, split) carrying all beams; num_beams 2 and 4) measured SLOWER at medium.en 4 x 4:
-        // 28.5 against 17.6 us per launch (per-row reading of 16 rows: 32.2), profiles/beam_cost.json -- it is kept as an A/B only:
-        // WT_BEAM_CROSS=grouped (read per decode, so one handle can time both: tools/beam_cost.py).
-        const char* form = tuning_env("WT_BEAM_CROSS");
-        int group = 0;
-        if (form && !strcmp(form, "grouped") && (beam.num_beams == 2 || beam.num_beams == 4) && !stream_mode) group = beam.num_beams;
-        if (group != e->beam_group) e->graph_valid = false;
-        e->beam_group = group;
-        if (beam.num_beams > 1 && e->nsplit_self != 1) { e->nsplit_self = 1; e->graph_valid = false; }   // the ancestry form is unsplit
-    }
-    {
-        const int rows = e->beam_group > 1 ? B / e->beam_group : B;   // blocks per head and split
-        const int ns = tuning_env("WT_NSPLIT_CROSS") ? atoi(tuning_env("WT_NSPLIT_CROSS")) : pick_splits(rows, e->H, e->S);
-        if (ns != e->nsplit_cross) e->graph_valid = false;
-        e->nsplit_cross = ns;
-    }
+    if (k.tt.n_sel > 0 && (rc = tt_reserve(e, k, s))) return rc;   // token-level timestamps: workspace and head tables of this decode
+    if (stream && (rc = stream_reserve(e, cfg.pool_rows, s))) return rc;
     e->epoch = e->epoch % 0xffff + 1;   // 1..65535: never the value of a freshly zeroed mailbox
     e->issued = 0;
-    e->stream_mode = stream_mode;
+    e->cfg = cfg;
     return WT_OK;
 }
 
 extern "C" int wt_decoder_set_timestamp_rules(wt_engine* e, const wt_timestamp_params* t) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: not a decoder engine");
     if (!t || !t->enabled) {
-        e->ts_req = wt_timestamp_params{0, 0, 0, 0, 0};
+        e->req.ts = wt_timestamp_params{0, 0, 0, 0, 0};
         return WT_OK;
     }
     if (t->timestamp_begin <= 0 || t->timestamp_begin >= e->V)
@@ -1164,15 +1044,15 @@ extern "C" int wt_decoder_set_timestamp_rules(wt_engine* e, const wt_timestamp_p
     if (t->no_timestamps_token_id < 0 || t->no_timestamps_token_id >= t->timestamp_begin)
         return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: no_timestamps_token_id %d outside [0, timestamp_begin=%d)", t->no_timestamps_token_id, t->timestamp_begin);
     if (t->begin_index < 2) return fail(WT_E_INVALID, "wt_decoder_set_timestamp_rules: begin_index %d < 2 (the prompt holds the start token)", t->begin_index);
-    e->ts_req = *t;
-    e->ts_req.enabled = 1;
+    e->req.ts = *t;
+    e->req.ts.enabled = 1;
     return WT_OK;
 }
 
 extern "C" int wt_decoder_set_beam_search(wt_engine* e, const wt_beam_params* b) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_beam_search: not a decoder engine");
     if (!b || b->num_beams <= 1) {
-        e->beam_req = wt_beam_params{1, 1.f, 0};
+        e->req.beam = wt_beam_params{1, 1.f, 0};
         return WT_OK;
     }
     if (b->num_beams > MAX_BEAMS) return fail(WT_E_UNSUPPORTED, "wt_decoder_set_beam_search: num_beams %d > %d", b->num_beams, MAX_BEAMS);
@@ -1180,14 +1060,14 @@ extern "C" int wt_decoder_set_beam_search(wt_engine* e, const wt_beam_params* b)
         return fail(WT_E_UNSUPPORTED, "wt_decoder_set_beam_search: early_stopping %d (0 or 1; \"never\" is not supported)", b->early_stopping);
     if (!(b->length_penalty == b->length_penalty) || fabsf(b->length_penalty) > 1e3f)
         return fail(WT_E_INVALID, "wt_decoder_set_beam_search: length_penalty %g", (double)b->length_penalty);
-    e->beam_req = *b;
+    e->req.beam = *b;
     return WT_OK;
 }
 
 extern "C" int wt_decoder_set_token_timestamps(wt_engine* e, const wt_token_timestamp_params* t) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: not a decoder engine");
     if (!t || t->n_heads <= 0) {
-        e->tt_req = wt_engine::TokTs{};
+        e->req.tt = DecodeRequest::TokTs{};
         return WT_OK;
     }
     if (t->n_heads > TT_MAX_HEADS) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: %d alignment heads > %d", t->n_heads, TT_MAX_HEADS);
@@ -1196,7 +1076,7 @@ extern "C" int wt_decoder_set_token_timestamps(wt_engine* e, const wt_token_time
         return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: median_filter_width %d (odd, 1 .. %d)", t->median_filter_width, TT_MAX_WIDTH);
     if (!(t->time_precision > 0.0) || !(t->time_precision < 1e6))
         return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: time_precision %g", t->time_precision);
-    wt_engine::TokTs tt;
+    DecodeRequest::TokTs tt;
     tt.n_sel = t->n_heads; tt.width = t->median_filter_width; tt.time_precision = t->time_precision;
     for (int i = 0; i < t->n_heads; ++i) {
         const int l = t->heads[2 * i], h = t->heads[2 * i + 1];
@@ -1206,19 +1086,19 @@ extern "C" int wt_decoder_set_token_timestamps(wt_engine* e, const wt_token_time
             if (tt.layer[j] == l && tt.head[j] == h) return fail(WT_E_INVALID, "wt_decoder_set_token_timestamps: alignment head (%d, %d) listed twice", l, h);
         tt.layer[i] = l; tt.head[i] = h;
     }
-    e->tt_req = tt;
+    e->req.tt = tt;
     return WT_OK;
 }
 
 extern "C" int wt_decoder_set_logprobs(wt_engine* e, const wt_logprob_params* p) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_logprobs: not a decoder engine");
     if (!p || !p->enabled) {
-        e->lp_req = wt_logprob_params{0, -1};
+        e->req.lp = wt_logprob_params{0, -1};
         return WT_OK;
     }
     if (p->no_speech_token_id < -1 || p->no_speech_token_id >= e->V)
         return fail(WT_E_INVALID, "wt_decoder_set_logprobs: no_speech_token_id %d outside [-1, V=%d)", p->no_speech_token_id, e->V);
-    e->lp_req = wt_logprob_params{1, p->no_speech_token_id};
+    e->req.lp = wt_logprob_params{1, p->no_speech_token_id};
     return WT_OK;
 }
 
@@ -1226,25 +1106,25 @@ extern "C" int wt_decoder_set_sampling(wt_engine* e, const wt_sampling_params* p
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_sampling: not a decoder engine");
     if (p && !(fabsf(p->temperature) <= 3.4028235e38f)) return fail(WT_E_INVALID, "wt_decoder_set_sampling: temperature is not finite");
     if (!p || !(p->temperature > 0.f)) {
-        e->samp_req_temp = 0.f;
-        e->samp_req_list = false;
-        e->samp_req_seeds.clear();
+        e->req.samp_temp = 0.f;
+        e->req.samp_list = false;
+        e->req.samp_seeds.clear();
         return WT_OK;
     }
     if (p->seeds && p->n_seeds < 1) return fail(WT_E_INVALID, "wt_decoder_set_sampling: a seed list of %d entries", p->n_seeds);
-    e->samp_req_temp = p->temperature;
-    e->samp_req_seed = p->seed;
-    e->samp_req_list = p->seeds != nullptr;
-    e->samp_req_seeds.clear();
-    if (p->seeds) e->samp_req_seeds.assign(p->seeds, p->seeds + p->n_seeds);
+    e->req.samp_temp = p->temperature;
+    e->req.samp_seed = p->seed;
+    e->req.samp_list = p->seeds != nullptr;
+    e->req.samp_seeds.clear();
+    if (p->seeds) e->req.samp_seeds.assign(p->seeds, p->seeds + p->n_seeds);
     return WT_OK;
 }
 
 extern "C" int wt_decoder_set_prompt(wt_engine* e, const wt_prompt_params* p) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_prompt: not a decoder engine");
     if (!p || p->len <= 0) {
-        e->prompt_req.clear();
-        e->prompt_req_rows = e->prompt_req_len = 0;
+        e->req.prompt.clear();
+        e->req.prompt_rows = e->req.prompt_len = 0;
         return WT_OK;
     }
     if (!p->ids || p->n_rows < 1) return fail(WT_E_INVALID, "wt_decoder_set_prompt: null ids or %d rows", p->n_rows);
@@ -1253,9 +1133,9 @@ extern "C" int wt_decoder_set_prompt(wt_engine* e, const wt_prompt_params* p) {
     for (size_t i = 0; i < n; ++i)
         if (p->ids[i] < 0 || p->ids[i] >= e->V)
             return fail(WT_E_INVALID, "wt_decoder_set_prompt: token %d (row %zu, position %zu) outside the vocabulary", p->ids[i], i / p->len, i % p->len);
-    e->prompt_req.assign(p->ids, p->ids + n);
-    e->prompt_req_rows = p->n_rows;
-    e->prompt_req_len = p->len;
+    e->req.prompt.assign(p->ids, p->ids + n);
+    e->req.prompt_rows = p->n_rows;
+    e->req.prompt_len = p->len;
     return WT_OK;
 }
 
@@ -1330,143 +1210,107 @@ static int enqueue_prefill(wt_engine* e, int B, int len, float* const* bufs, con
     return WT_OK;
 }
 
-// the log-probability setting of the decode that is starting (a changed one re-captures the step graphs)
-static void lp_apply(wt_engine* e, const wt_logprob_params lp) {
-    if (memcmp(&e->lp_cur, &lp, sizeof lp) != 0) e->graph_valid = false;
-    e->lp_cur = lp;
-}
-
 static void fill_select_params(wt_engine* e, SelectParams& sp);
 
 extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, const wt_greedy_params* p, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_begin: not a decoder engine");
     if (!enc_hidden || !p || B < 1) return fail(WT_E_INVALID, "wt_decoder_begin: bad arguments");
-    // beam search: `B` utterances decode as B * num_beams rows, [utterance][beam]
-    const wt_beam_params beam = e->beam_req;
-    const int nb = beam.num_beams > 1 ? beam.num_beams : 1, U = B;
-    if (nb > 1) {
-        if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and timestamp mode cannot be combined");
-        if (e->tt_req.n_sel > 0)
-            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token-level timestamps cannot be combined (no beam_indices)");
-        if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
-            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: logits_trace / force_eos_step(s) are not available with beam search");
-        if (e->lp_req.enabled)
-            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token log-probabilities cannot be combined (wt_decoder_read_beam_scores is the beams' score)");
-        if (e->samp_req_temp > 0.f)
-            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and temperature sampling cannot be combined");
-        if (U * nb > MAX_ROWS) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", U, nb, MAX_ROWS);
-        B = U * nb;
-    }
-    const int plen = e->prompt_req_len, prows = e->prompt_req_rows;
-    if (plen > 0) {
-        if (e->w_half || e->kv_esz != 4)
-            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: decoder prompts need an fp32 decoder engine (the prefill's GEMMs and attention are fp32)");
-        if (nb > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and beam search cannot be combined");
-        if (e->tt_req.n_sel > 0)
-            return fail(WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and token-level timestamps cannot be combined (their query history is "
-                                          "indexed by step and sized by the sequence length)");
-        if (prows != 1 && prows < B) return fail(WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_prompt gave %d prompt rows for a batch of %d", prows, B);
-        if (plen + 2 > p->max_length)
-            return fail(WT_E_INVALID, "wt_decoder_begin: %d prompt tokens + the start token + one generated token > max_length %d", plen, p->max_length);
-    }
-    const float samp_temp = e->samp_req_temp;
-    if (samp_temp > 0.f && e->samp_req_list && (int)e->samp_req_seeds.size() < B)
-        return fail(WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_sampling gave %d seeds for a batch of %d", (int)e->samp_req_seeds.size(), B);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    int rc = decode_setup(e, B, p, 0, false, s, "wt_decoder_begin", nb > 1 ? beam : wt_beam_params{1, 1.f, 0});
+    int rc = decode_setup(e, B, p, 0, false, s);
     if (rc) return rc;
-    e->beam_U = U;
-    {   // temperature sampling runs the log-probability mode's kernels in their sampling form
-        wt_logprob_params lp = e->lp_req;
-        if (samp_temp > 0.f) lp.enabled = 1;
-        lp_apply(e, lp);
-        if (samp_temp != e->samp_cur_temp) e->graph_valid = false;   // the step graph carries the temperature
-        e->samp_cur_temp = samp_temp;
-        if (samp_temp > 0.f) {
-            std::vector<unsigned long long>& h = e->samp_req_seeds;   // (kept alive by the handle: the copy below may read it later)
-            if (!e->samp_req_list) {
-                h.resize(B);
-                for (int b = 0; b < B; ++b) h[b] = e->samp_req_seed + (unsigned long long)b;
-            }
-            HIPCHK(hipMemcpyAsync(e->samp_seeds, h.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
+    const DecodeConfig& c = e->cfg;
+    const StepKey& k = c.key;
+    B = k.B;   // beam search: the utterances decode as U * num_beams rows, [utterance][beam]
+    if (k.samp_temp > 0.f) {   // (pageable sources kept alive by the handle: the copy below may read them later)
+        if (!e->req.samp_list) {
+            e->h_seeds.resize(B);
+            for (int b = 0; b < B; ++b) e->h_seeds[b] = e->req.samp_seed + (unsigned long long)b;
         }
+        const std::vector<unsigned long long>& h = e->req.samp_list ? e->req.samp_seeds : e->h_seeds;
+        HIPCHK(hipMemcpyAsync(e->samp_seeds, h.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
     }
-    if (e->lp_cur.enabled) {   // position 0, the positions behind an EOS and the sums start at zero
-        HIPCHK(hipMemsetAsync(e->lp_tok, 0, (size_t)B * p->max_length * 4, s));
+    if (k.lp.enabled) {   // position 0, the positions behind an EOS and the sums start at zero
+        HIPCHK(hipMemsetAsync(e->lp_tok, 0, (size_t)B * k.max_length * 4, s));
         HIPCHK(hipMemsetAsync(e->lp_sum, 0, (size_t)B * 4, s));
         HIPCHK(hipMemsetAsync(e->lp_nsp, 0, (size_t)B * 4, s));
         HIPCHK(hipMemsetAsync(e->lp_side, 0, (size_t)B * 2 * 4, s));
     }
-    LAUNCH(launch_dec_init(e->st, e->ids, e->unfinished, B, p->max_length, p->decoder_start_token_id, e->epoch, s));
-    if (nb > 1) {
+    LAUNCH(launch_dec_init(e->st, e->ids, e->unfinished, B, k.max_length, k.start_token, e->epoch, s));
+    if (k.beam.num_beams > 1) {
         SelectParams sp;
         fill_select_params(e, sp);
         LAUNCH(launch_beam_init(sp, s));
     }
+    const int plen = c.prompt_len;
     float* pf_bufs[6];
     int* pf_ids = nullptr;
     if (plen > 0) {   // the prompt's ids and the state behind it; the step-0 input below is then the start token at position plen
         rc = prefill_reserve(e, B, plen, s, pf_bufs, &pf_ids);
         if (rc) return rc;
         // (pageable source kept alive by the handle, as the sampling seeds above)
-        HIPCHK(hipMemcpyAsync(pf_ids, e->prompt_req.data(), (size_t)(prows == 1 ? 1 : B) * plen * 4, hipMemcpyHostToDevice, s));
-        LAUNCH(launch_prefill_state(e->st, e->ids, pf_ids, prows == 1 ? 1 : B, plen, B, p->max_length, p->decoder_start_token_id, s));
+        HIPCHK(hipMemcpyAsync(pf_ids, e->req.prompt.data(), (size_t)c.prompt_rows * plen * 4, hipMemcpyHostToDevice, s));
+        LAUNCH(launch_prefill_state(e->st, e->ids, pf_ids, c.prompt_rows, plen, B, k.max_length, k.start_token, s));
     }
-    e->prompt_len = plen;
-    LAUNCH(launch_dec_embed(e->ids, p->max_length, e->tok_emb, e->pos_emb, e->dh, B, e->d, e->st, s, e->w_half));  // input of step 0
+    LAUNCH(launch_dec_embed(e->ids, k.max_length, e->tok_emb, e->pos_emb, e->dh, B, e->d, e->st, s, e->w_half));  // input of step 0
     // the beams of an utterance attend over the same encoder memory: its cross K/V are projected once, into cache row u
-    rc = cross_kv_project(e, enc_hidden, U, e->S, 0, e->cross_k, e->cross_v, e->kv_esz, s, e->cross_rows, 0);
+    rc = cross_kv_project(e, enc_hidden, c.U, e->S, 0, e->cross_k, e->cross_v, e->kv_esz, s, e->cross_rows, 0);
     if (rc) return rc;
     if (plen > 0) {   // behind the cross K/V projection: the prefill's cross attention reads this decode's cross caches
-        rc = enqueue_prefill(e, B, plen, pf_bufs, pf_ids, prows == 1 ? 1 : B, s);
+        rc = enqueue_prefill(e, B, plen, pf_bufs, pf_ids, c.prompt_rows, s);
         if (rc) return rc;
     }
     e->begun = true;
     return WT_OK;
 }
 
-static bool beam_on(const wt_engine* e) { return e->beam_cur.num_beams > 1 && !e->stream_mode; }
-static bool tt_on(const wt_engine* e) { return e->tt_cur.n_sel > 0 && !e->stream_mode; }
-
 static void fill_select_params(wt_engine* e, SelectParams& sp) {
-    greedy_select_params(sp, e->logits, e->mask, e->forced, e->ids, e->unfinished, e->st, e->trace, e->sel_val, e->sel_idx, e->tok_emb, e->pos_emb,
-                         e->dh, e->d, e->w_half, e->B, e->V, e->max_length, e->begin_index, e->eos, e->pad, e->force_eos_step,
-                         e->force_rows_on ? e->force_rows : nullptr, e->mailbox_dev, e->start_token);
-    if (e->ts_cur.enabled && !e->stream_mode) {
-        sp.ts_on = 1; sp.no_ts = e->ts_cur.no_timestamps_token_id; sp.tb = e->ts_cur.timestamp_begin;
-        sp.ts_begin_index = e->ts_cur.begin_index; sp.max_init = e->ts_cur.max_initial_timestamp_index; sp.ts_part = e->ts_part;
+    const StepKey& k = e->cfg.key;
+    greedy_select_params(sp, e->logits, e->mask, e->forced, e->ids, e->unfinished, e->st, k.logits_trace, e->sel_val, e->sel_idx, e->tok_emb, e->pos_emb,
+                         e->dh, e->d, e->w_half, k.B, e->V, k.max_length, k.begin_index, k.eos, k.pad, k.force_eos_step,
+                         k.force_rows_on ? e->force_rows : nullptr, e->mailbox_dev, k.start_token);
+    if (k.ts.enabled) {
+        sp.ts_on = 1; sp.no_ts = k.ts.no_timestamps_token_id; sp.tb = k.ts.timestamp_begin;
+        sp.ts_begin_index = k.ts.begin_index; sp.max_init = k.ts.max_initial_timestamp_index; sp.ts_part = e->ts_part;
     }
-    if (beam_on(e)) {
+    if (k.beam.num_beams > 1) {
         sp.beam_on = 1; sp.beam = e->beam_dev;
-        sp.beam.nb = e->beam_cur.num_beams; sp.beam.U = e->beam_U; sp.beam.length_penalty = e->beam_cur.length_penalty;
-        sp.beam.early_stopping = e->beam_cur.early_stopping;
+        sp.beam.nb = k.beam.num_beams; sp.beam.U = e->cfg.U; sp.beam.length_penalty = k.beam.length_penalty;
+        sp.beam.early_stopping = k.beam.early_stopping;
     }
-    if (e->lp_cur.enabled && !e->stream_mode) {
-        sp.lp_on = 1; sp.lp_ns = e->lp_cur.no_speech_token_id; sp.lp_part = e->lp_part; sp.lp_side = e->lp_side; sp.lp_tok = e->lp_tok;
+    if (k.lp.enabled) {
+        sp.lp_on = 1; sp.lp_ns = k.lp.no_speech_token_id; sp.lp_part = e->lp_part; sp.lp_side = e->lp_side; sp.lp_tok = e->lp_tok;
         sp.lp_sum = e->lp_sum; sp.lp_nsp = e->lp_nsp;
-        if (e->samp_cur_temp > 0.f) {
-            sp.samp_on = 1; sp.samp_temp = e->samp_cur_temp; sp.samp_seeds = e->samp_seeds; sp.samp_sc = e->samp_sc; sp.samp_ts = e->samp_ts;
+        if (k.samp_temp > 0.f) {
+            sp.samp_on = 1; sp.samp_temp = k.samp_temp; sp.samp_seeds = e->samp_seeds; sp.samp_sc = e->samp_sc; sp.samp_ts = e->samp_ts;
             sp.samp_K = e->d; sp.samp_parts_cap = SEL_PARTS_CAP;
         }
     }
-    if (e->stream_mode) {
-        sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1; sp.force_eos_rows = nullptr; sp.trace = nullptr;
+    if (e->cfg.stream) {
+        sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1;
     }
 }
 
-// variant bit 0: finished / idle rows stream no K/V (`alive`); bit 1: the continuous mode's graph (per-slot cross-cache rows and state)
-static int enqueue_fast_step(wt_engine* e, hipStream_t s, int variant = 0) {
+// the StepIO of one step of the decode in flight over the resident caches.  variant bit 0: finished / idle rows stream no K/V (`alive`);
+// bit 1: the continuous mode's graph (per-slot cross-cache rows and state)
+static StepIO step_io(const wt_engine* e, int variant) {
+    const StepKey& k = e->cfg.key;
     StepIO io;
     io.alive = (variant & 1) ? e->unfinished : nullptr;
-    io.ids = e->ids; io.ids_ld = e->max_length; io.self_k = e->self_k; io.self_v = e->self_v; io.self_cap = e->T;
-    io.cross_k = e->cross_k; io.cross_v = e->cross_v; io.cross_rows = e->cross_rows; io.logits = e->logits; io.B = e->B; io.kv_esz = e->kv_esz;
+    io.ids = e->ids; io.ids_ld = k.max_length; io.self_k = e->self_k; io.self_v = e->self_v; io.self_cap = e->T;
+    io.cross_k = e->cross_k; io.cross_v = e->cross_v; io.cross_rows = e->cross_rows; io.logits = e->logits; io.B = k.B; io.kv_esz = e->kv_esz;
     io.slot_row = (variant & 2) ? e->st->slot_row : nullptr;   // (address arithmetic on a device pointer: nothing is dereferenced here)
-    if (beam_on(e)) { io.slot_row = e->beam_dev.urow; io.anc = e->beam_dev.anc; io.anc_ld = e->beam_dev.anc_ld; io.group = e->beam_group; }
-    if (tt_on(e)) { io.qh = e->tt_qh; io.qh_sel = e->tt_sel; io.qh_rows = e->tt_rows; io.qh_steps = e->tt_steps; }
-    io.nsplit_self = e->nsplit_self; io.nsplit_cross = e->nsplit_cross;
+    if (k.beam.num_beams > 1) { io.slot_row = e->beam_dev.urow; io.anc = e->beam_dev.anc; io.anc_ld = e->beam_dev.anc_ld; io.group = k.beam_group; }
+    if (k.tt.n_sel > 0) { io.qh = e->tt_qh; io.qh_sel = e->tt_sel; io.qh_rows = k.tt_rows; io.qh_steps = k.tt_steps; }
+    io.nsplit_self = k.nsplit_self; io.nsplit_cross = k.nsplit_cross; io.nt = k.nt_loads;
     io.embed = false;  // dh already holds this step's input: written by wt_decoder_begin (step 0) or by the previous greedy_finish
+    io.argmax = nullptr; io.argmax_parts = nullptr;
+    return io;
+}
+
+static int enqueue_fast_step(wt_engine* e, hipStream_t s, int variant = 0) {
+    StepIO io = step_io(e, variant);
     static const bool fuse = tuning_env("WT_NO_FUSED_ARGMAX") == nullptr;  // A/B switch: logits to HBM + greedy_select_kernel
     SelectParams sp;
     fill_select_params(e, sp);
@@ -1491,9 +1335,11 @@ static std::mutex g_capture_mutex;
 // no K/V (wt_decoder_run switches to it once the mailbox reports a finished row; never with a logits trace, which records every
 // row's logits at every step as the reference computes them).  The continuous mode replays variants 2 / 3.
 static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant = 0) {
-    if (e->trace || beam_on(e)) variant = 0;   // (beam search: one graph; a finished utterance's rows keep attending)
-    if (tt_on(e)) variant = 0;   // token-level timestamps: finished rows keep stepping on pad input, their steps are part of the alignment
-    if (e->stream_mode) variant |= 2;
+    StepKey k = e->cfg.key;
+    k.workspace_gen = e->ws_gen;   // as it stands NOW: a (re)allocation behind the last begin must not replay graphs into freed memory
+    if (k.logits_trace || k.beam.num_beams > 1) variant = 0;   // (beam search: one graph; a finished utterance's rows keep attending)
+    if (k.tt.n_sel > 0) variant = 0;   // token-level timestamps: finished rows keep stepping on pad input, their steps are part of the alignment
+    if (e->cfg.stream) variant |= 2;
     if (e->profiling || !e->use_graph) {  // eager: per-kernel event timers need real launches
         for (int i = 0; i < n_steps; ++i) {
             int rc = enqueue_fast_step(e, s, variant);
@@ -1505,13 +1351,13 @@ static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant =
     // The step graph is CAPTURED on the engine's own stream (the caller's may be the NULL stream, which cannot be captured;
     // capturing executes nothing) and REPLAYED on the caller's stream: a replay on a second stream measured 5 % slower
     // per step (1.69 vs 1.60 ms, medium.en B=8) than on the stream the rest of the pass already runs on.
-    if (!e->graph_valid) {
+    if (k != e->graph_key) {   // the graphs bake in exactly what the key holds (host_logic.h: StepKey)
         for (int v = 0; v < wt_engine::N_GRAPHS; ++v) {
             if (e->graph_exec[v]) { hipGraphExecDestroy(e->graph_exec[v]); e->graph_exec[v] = nullptr; }
             if (e->graph[v]) { hipGraphDestroy(e->graph[v]); e->graph[v] = nullptr; }
             e->graph_ok[v] = false;
         }
-        e->graph_valid = true;
+        e->graph_key = k;
     }
     if (!e->graph_ok[variant]) {
         std::lock_guard<std::mutex> lock(g_capture_mutex);
@@ -1531,6 +1377,7 @@ static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant =
             return fail(WT_E_HIP, "hipGraphInstantiate failed: %s", hipGetErrorString(ie));
         }
         e->graph_ok[variant] = true;
+        e->graph_captures += 1;
     }
     for (int i = 0; i < n_steps; ++i) {
         HIPCHK(hipGraphLaunch(e->graph_exec[variant], s));
@@ -1548,38 +1395,12 @@ static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant =
 extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, const wt_greedy_params* p, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_stream_begin: not a decoder engine");
     if (!p || slots < 1) return fail(WT_E_INVALID, "wt_decoder_stream_begin: bad arguments");
-    if (pool_rows <= 0) pool_rows = 4 * slots;     // slots decoding + 3 x slots prepared ahead
-    if (pool_rows < slots + 1 || pool_rows > STREAM_QCAP) return fail(WT_E_INVALID, "wt_decoder_stream_begin: pool of %d rows outside [slots + 1, %d]", pool_rows, STREAM_QCAP);
-    if (e->ts_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: timestamp mode is a batch-decode feature (wt_decoder_begin)");
-    if (e->beam_req.num_beams > 1) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: beam search is a batch-decode feature (wt_decoder_begin)");
-    if (e->tt_req.n_sel > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token-level timestamps are a batch-decode feature (wt_decoder_begin)");
-    if (e->lp_req.enabled) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token log-probabilities are a batch-decode feature (wt_decoder_begin)");
-    if (e->samp_req_temp > 0.f) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: temperature sampling is a batch-decode feature (wt_decoder_begin)");
-    if (e->prompt_req_len > 0) return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: decoder prompts are a batch-decode feature (wt_decoder_begin)");
-    if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
-        return fail(WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    int rc = decode_setup(e, slots, p, pool_rows, true, s, "wt_decoder_stream_begin");
+    int rc = decode_setup(e, slots, p, pool_rows, true, s);
     if (rc) return rc;
-    lp_apply(e, wt_logprob_params{0, -1});
-    if (e->samp_cur_temp != 0.f) { e->samp_cur_temp = 0.f; e->graph_valid = false; }
-    if (pool_rows > e->h_pool_cap || e->dec_maxlen_cap > e->h_ml_cap) {   // pinned report area: ids and final lengths per pool row
-        HIPCHK(hipStreamSynchronize(s));   // no step of an earlier stream may still write the old area
-        const int rows = pool_rows > e->h_pool_cap ? pool_rows : e->h_pool_cap;
-        if (e->h_ids) { hipHostFree(e->h_ids); e->h_ids = nullptr; }
-        if (e->h_len) { hipHostFree(e->h_len); e->h_len = nullptr; }
-        e->h_pool_cap = 0;
-        HIPCHK(hipHostMalloc((void**)&e->h_ids, (size_t)rows * e->dec_maxlen_cap * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostMalloc((void**)&e->h_len, (size_t)rows * 4, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_ids_dev, e->h_ids, 0));
-        HIPCHK(hipHostGetDevicePointer((void**)&e->h_len_dev, e->h_len, 0));
-        e->h_pool_cap = rows;
-        e->h_ml_cap = e->dec_maxlen_cap;
-        e->graph_valid = false;   // the step graph carries these addresses
-    }
-    e->pool_rows = pool_rows;
+    pool_rows = e->cfg.pool_rows;
     e->pool_state.assign(pool_rows, 0);
     e->submitted = e->finished_seen = e->admitted_seen = 0;
     for (int r = 0; r < pool_rows; ++r) __atomic_store_n(e->h_len + r, 0, __ATOMIC_RELAXED);
@@ -1590,7 +1411,7 @@ extern "C" int wt_decoder_stream_begin(wt_engine* e, int slots, int pool_rows, c
 
 extern "C" int wt_decoder_stream_submit(wt_engine* e, const float* enc_hidden, int n, const int32_t* force_eos_steps, int32_t* handles,
                                         void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !e->stream_mode) return fail(WT_E_STATE, "wt_decoder_stream_submit: no stream open (wt_decoder_stream_begin)");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !e->cfg.stream) return fail(WT_E_STATE, "wt_decoder_stream_submit: no stream open (wt_decoder_stream_begin)");
     if (!enc_hidden || !handles || n < 1 || n > MAX_ROWS) return fail(WT_E_INVALID, "wt_decoder_stream_submit: 1 .. %d utterances per call", MAX_ROWS);
     if (e->submitted - e->admitted_seen + n > STREAM_QCAP) return fail(WT_E_STATE, "wt_decoder_stream_submit: waiting queue full");
     DeviceGuard guard(e->device);
@@ -1598,7 +1419,7 @@ extern "C" int wt_decoder_stream_submit(wt_engine* e, const float* enc_hidden, i
     hipStream_t s = (hipStream_t)stream;
     // pool rows for the n utterances: as few contiguous runs as the free list allows (one batched K/V projection per run and layer)
     std::vector<int> rows;
-    for (int r = 0; r < e->pool_rows && (int)rows.size() < n; ++r)
+    for (int r = 0; r < e->cfg.pool_rows && (int)rows.size() < n; ++r)
         if (e->pool_state[r] == 0) rows.push_back(r);
     if ((int)rows.size() < n) return fail(WT_E_STATE, "wt_decoder_stream_submit: %d free cache rows for %d utterances (collect finished ones first)", (int)rows.size(), n);
     StreamPublish pub;
@@ -1630,7 +1451,7 @@ extern "C" int wt_decoder_stream_submit(wt_engine* e, const float* enc_hidden, i
 // newly finished utterances (their pinned length word has become non-zero): state 1 -> 2
 static int stream_scan_finished(wt_engine* e) {
     int n = 0;
-    for (int r = 0; r < e->pool_rows; ++r)
+    for (int r = 0; r < e->cfg.pool_rows; ++r)
         if (e->pool_state[r] == 1 && __atomic_load_n(e->h_len + r, __ATOMIC_ACQUIRE) != 0) {
             e->pool_state[r] = 2;
             ++n;
@@ -1642,11 +1463,11 @@ static int stream_scan_finished(wt_engine* e) {
 // Steps until (a) every submitted utterance has finished, or (b) fewer than `min_waiting` submitted utterances are still waiting for a
 // slot (min_waiting > 0: the caller has more to submit and wants the queue topped up).  Follows the mailbox like wt_decoder_run.
 extern "C" int wt_decoder_stream_run(wt_engine* e, int min_waiting, int lookahead, int* n_finished, int* n_waiting, int* n_steps, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !e->stream_mode) return fail(WT_E_STATE, "wt_decoder_stream_run: no stream open (wt_decoder_stream_begin)");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !e->cfg.stream) return fail(WT_E_STATE, "wt_decoder_stream_run: no stream open (wt_decoder_stream_begin)");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    if (lookahead <= 0) lookahead = e->nt_loads ? 1 : 3;
+    if (lookahead <= 0) lookahead = e->cfg.key.nt_loads ? 1 : 3;
     if (lookahead > 64) lookahead = 64;
     int spins = 0, slices = 0;
     unsigned long long last = ~0ull;
@@ -1668,7 +1489,7 @@ extern "C" int wt_decoder_stream_run(wt_engine* e, int min_waiting, int lookahea
         if (min_waiting > 0 && waiting_ub < min_waiting) break;
         if (e->issued - retired <= lookahead) {
             // idle slots with nothing waiting (the tail of the workload): the graph whose attention skips them
-            const unsigned full = (1u << e->B) - 1u;
+            const unsigned full = (1u << e->cfg.key.B) - 1u;
             const int variant = (mine && retired > 0 && ((unsigned)mb & 0xffffu) != full && waiting_ub == 0) ? 1 : 0;
             const int rc = enqueue_steps(e, 1, s, variant);
             if (rc) return rc;
@@ -1703,15 +1524,15 @@ extern "C" int wt_decoder_stream_run(wt_engine* e, int min_waiting, int lookahea
 // waiting or decoding (ids_out untouched).  With ids_out != NULL a finished utterance's ids are copied to HOST memory (capacity `cap`
 // >= max_length int32) and its cache row is released for the next submit.
 extern "C" int wt_decoder_stream_collect(wt_engine* e, int handle, int32_t* ids_out, int cap, int* len) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->stream_mode) return fail(WT_E_STATE, "wt_decoder_stream_collect: no stream open");
-    if (handle < 0 || handle >= e->pool_rows || !len) return fail(WT_E_INVALID, "wt_decoder_stream_collect: bad handle %d", handle);
+    if (!e || e->kind != WT_KIND_DECODER || !e->cfg.stream) return fail(WT_E_STATE, "wt_decoder_stream_collect: no stream open");
+    if (handle < 0 || handle >= e->cfg.pool_rows || !len) return fail(WT_E_INVALID, "wt_decoder_stream_collect: bad handle %d", handle);
     if (e->pool_state[handle] == 0) return fail(WT_E_STATE, "wt_decoder_stream_collect: row %d holds no utterance", handle);
     const int n = __atomic_load_n(e->h_len + handle, __ATOMIC_ACQUIRE);
     *len = n;
     if (n == 0 || !ids_out) return WT_OK;
     if (cap < n) return fail(WT_E_INVALID, "wt_decoder_stream_collect: %d ids, capacity %d", n, cap);
     if (e->pool_state[handle] == 1) { e->pool_state[handle] = 2; e->finished_seen += 1; }
-    memcpy(ids_out, e->h_ids + (size_t)handle * e->max_length, (size_t)n * 4);   // row stride of stream_finish_kernel: this stream's max_length
+    memcpy(ids_out, e->h_ids + (size_t)handle * e->cfg.key.max_length, (size_t)n * 4);   // row stride of stream_finish_kernel: this stream's max_length
     e->pool_state[handle] = 0;
     return WT_OK;
 }
@@ -1733,13 +1554,13 @@ extern "C" int wt_decoder_steps(wt_engine* e, int n_steps, void* stream) {
 extern "C" int wt_decoder_run(wt_engine* e, int lookahead, int* cur_len, int* n_unfinished, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_run: not a decoder engine");
     if (!e->begun) return fail(WT_E_STATE, "wt_decoder_run called before wt_decoder_begin");
-    if (e->stream_mode) return fail(WT_E_STATE, "wt_decoder_run: a continuous decode is open on this handle (wt_decoder_stream_run)");
+    if (e->cfg.stream) return fail(WT_E_STATE, "wt_decoder_run: a continuous decode is open on this handle (wt_decoder_stream_run)");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    if (lookahead <= 0) lookahead = e->nt_loads ? 1 : 3;   // small models: a step is 0.15-0.3 ms, keep more of them queued
+    if (lookahead <= 0) lookahead = e->cfg.key.nt_loads ? 1 : 3;   // small models: a step is 0.15-0.3 ms, keep more of them queued
     if (lookahead > 64) lookahead = 64;
-    const int max_steps = e->max_length - 1 - e->prompt_len;   // MaxLengthCriteria fires at the latest after this many steps
+    const int max_steps = e->cfg.key.max_length - 1 - e->cfg.prompt_len;   // MaxLengthCriteria fires at the latest after this many steps
     unsigned long long mb = 0;
     int spins = 0, slices = 0;   // since the last launch: busy-wait iterations, then 20 us sleep slices
     for (;;) {
@@ -1751,7 +1572,7 @@ extern "C" int wt_decoder_run(wt_engine* e, int lookahead, int* cur_len, int* n_
         if (mine && ((mb >> 31) & 1)) break;
         if (e->issued < max_steps && e->issued - retired <= lookahead) {
             // a row has finished (the word's unfinished mask lost a bit): from here on replay the graph whose attention skips such rows
-            const unsigned full = (1u << e->B) - 1u;
+            const unsigned full = (1u << e->cfg.key.B) - 1u;
             const int variant = (mine && retired > 0 && ((unsigned)mb & 0xffffu) != full) ? 1 : 0;
             int rc = enqueue_steps(e, 1, s, variant);
             if (rc) return rc;
@@ -1801,89 +1622,89 @@ extern "C" int wt_decoder_poll(wt_engine* e, int* cur_len, int* n_unfinished, in
 
 extern "C" int wt_decoder_read_ids(wt_engine* e, int32_t* ids_out, int ld, void* stream) {
     if (!e || e->kind != WT_KIND_DECODER || !e->begun) return fail(WT_E_STATE, "wt_decoder_read_ids: no decode in flight");
-    if (!ids_out || ld < e->max_length) return fail(WT_E_INVALID, "wt_decoder_read_ids: row stride %d < max_length %d", ld, e->max_length);
+    if (!ids_out || ld < e->cfg.key.max_length) return fail(WT_E_INVALID, "wt_decoder_read_ids: row stride %d < max_length %d", ld, e->cfg.key.max_length);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
-    if (beam_on(e)) {   // the best hypothesis of every utterance: finalize runs on the stream, behind the steps
+    if (e->cfg.key.beam.num_beams > 1) {   // the best hypothesis of every utterance: finalize runs on the stream, behind the steps
         SelectParams sp;
         fill_select_params(e, sp);
         LAUNCH(launch_beam_finalize(sp, (hipStream_t)stream));
-        HIPCHK(hipMemcpy2DAsync(ids_out, (size_t)ld * 4, e->beam_dev.out_ids, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->beam_U,
+        HIPCHK(hipMemcpy2DAsync(ids_out, (size_t)ld * 4, e->beam_dev.out_ids, (size_t)e->cfg.key.max_length * 4, (size_t)e->cfg.key.max_length * 4, e->cfg.U,
                                 hipMemcpyDeviceToDevice, (hipStream_t)stream));
         return WT_OK;
     }
-    HIPCHK(hipMemcpy2DAsync(ids_out, (size_t)ld * 4, e->ids, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->B,
+    HIPCHK(hipMemcpy2DAsync(ids_out, (size_t)ld * 4, e->ids, (size_t)e->cfg.key.max_length * 4, (size_t)e->cfg.key.max_length * 4, e->cfg.key.B,
                             hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 
 extern "C" int wt_decoder_read_beam_scores(wt_engine* e, float* scores_out, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !beam_on(e)) return fail(WT_E_STATE, "wt_decoder_read_beam_scores: no beam decode in flight");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.beam.num_beams <= 1) return fail(WT_E_STATE, "wt_decoder_read_beam_scores: no beam decode in flight");
     if (!scores_out) return fail(WT_E_INVALID, "wt_decoder_read_beam_scores: null output");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     SelectParams sp;
     fill_select_params(e, sp);
     LAUNCH(launch_beam_finalize(sp, (hipStream_t)stream));
-    HIPCHK(hipMemcpyAsync(scores_out, e->beam_dev.out_scores, (size_t)e->beam_U * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(scores_out, e->beam_dev.out_scores, (size_t)e->cfg.U * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 
 extern "C" int wt_decoder_read_logprobs(wt_engine* e, float* token_logprobs, int ld, float* sum_logprob, float* no_speech_prob, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->stream_mode || !e->lp_cur.enabled)
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !e->cfg.key.lp.enabled)
         return fail(WT_E_STATE, "wt_decoder_read_logprobs: no decode with token log-probabilities in flight (wt_decoder_set_logprobs, then wt_decoder_begin)");
-    if (!token_logprobs || !sum_logprob || ld < e->max_length)
-        return fail(WT_E_INVALID, "wt_decoder_read_logprobs: null output or row stride %d < max_length %d", ld, e->max_length);
-    if (no_speech_prob && e->lp_cur.no_speech_token_id < 0)
+    if (!token_logprobs || !sum_logprob || ld < e->cfg.key.max_length)
+        return fail(WT_E_INVALID, "wt_decoder_read_logprobs: null output or row stride %d < max_length %d", ld, e->cfg.key.max_length);
+    if (no_speech_prob && e->cfg.key.lp.no_speech_token_id < 0)
         return fail(WT_E_INVALID, "wt_decoder_read_logprobs: no_speech_prob was not requested (no_speech_token_id -1)");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipMemcpy2DAsync(token_logprobs, (size_t)ld * 4, e->lp_tok, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->B, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sum_logprob, e->lp_sum, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
-    if (no_speech_prob) HIPCHK(hipMemcpyAsync(no_speech_prob, e->lp_nsp, (size_t)e->B * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(token_logprobs, (size_t)ld * 4, e->lp_tok, (size_t)e->cfg.key.max_length * 4, (size_t)e->cfg.key.max_length * 4, e->cfg.key.B, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sum_logprob, e->lp_sum, (size_t)e->cfg.key.B * 4, hipMemcpyDeviceToDevice, s));
+    if (no_speech_prob) HIPCHK(hipMemcpyAsync(no_speech_prob, e->lp_nsp, (size_t)e->cfg.key.B * 4, hipMemcpyDeviceToDevice, s));
     return WT_OK;
 }
 
 // the post-pass of the token-level timestamps over the decode in flight: q_hist x resident cross-K -> matrix -> DTW -> seconds
 static void tt_fill(const wt_engine* e, TokTsParams& p) {
     memset(&p, 0, sizeof p);
-    const wt_engine::TokTs& tt = e->tt_cur;
-    p.q_hist = e->tt_qh; p.qh_rows = e->tt_rows; p.qh_steps = e->tt_steps;
+    const StepKey& k = e->cfg.key;
+    p.q_hist = e->tt_qh; p.qh_rows = e->cfg.key.tt_rows; p.qh_steps = e->cfg.key.tt_steps;
     p.cross_k = e->cross_k; p.kv_half = e->kv_esz == 2 ? 1 : 0; p.cross_rows = e->cross_rows; p.H = e->H; p.S = e->S;
-    p.n_sel = tt.n_sel;
-    memcpy(p.layer, tt.layer, sizeof p.layer);
-    memcpy(p.head, tt.head, sizeof p.head);
-    p.width = tt.width; p.time_precision = tt.time_precision;
-    p.st = e->st; p.n_cap = e->tt_steps; p.B = e->B;
+    p.n_sel = k.tt.n_sel;
+    memcpy(p.layer, k.tt.layer, sizeof p.layer);
+    memcpy(p.head, k.tt.head, sizeof p.head);
+    p.width = e->cfg.tt_width; p.time_precision = e->cfg.tt_time_precision;
+    p.st = e->st; p.n_cap = e->cfg.key.tt_steps; p.B = e->cfg.key.B;
     p.W = e->tt_W; p.mean = e->tt_mean; p.sdev = e->tt_sdev; p.matrix = e->tt_matrix; p.trace = e->tt_trace; p.trace_ld = tt_trace_ld(e->S);
-    p.out = e->tt_out; p.out_ld = e->max_length;
+    p.out = e->tt_out; p.out_ld = e->cfg.key.max_length;
 }
 extern "C" int wt_decoder_read_token_timestamps(wt_engine* e, float* out, int ld, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e))
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.tt.n_sel == 0)
         return fail(WT_E_STATE, "wt_decoder_read_token_timestamps: no decode with token-level timestamps in flight");
-    if (!out || ld < e->max_length) return fail(WT_E_INVALID, "wt_decoder_read_token_timestamps: row stride %d < max_length %d", ld, e->max_length);
+    if (!out || ld < e->cfg.key.max_length) return fail(WT_E_INVALID, "wt_decoder_read_token_timestamps: row stride %d < max_length %d", ld, e->cfg.key.max_length);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
     TokTsParams p;
     tt_fill(e, p);
-    for (int b = 0; b < e->B; ++b) LAUNCH(launch_tt_matrix(p, b, s));
+    for (int b = 0; b < e->cfg.key.B; ++b) LAUNCH(launch_tt_matrix(p, b, s));
     LAUNCH(launch_tt_dtw(p, s));
-    HIPCHK(hipMemcpy2DAsync(out, (size_t)ld * 4, e->tt_out, (size_t)e->max_length * 4, (size_t)e->max_length * 4, e->B, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(out, (size_t)ld * 4, e->tt_out, (size_t)e->cfg.key.max_length * 4, (size_t)e->cfg.key.max_length * 4, e->cfg.key.B, hipMemcpyDeviceToDevice, s));
     return WT_OK;
 }
 // the two halves of the post-pass alone, for timing (tools/token_timestamp_cost.py): which = 1 the matrix launches of every utterance,
 // 2 the DTW launch (over the matrix as it stands); and the bytes of the mode's device allocation
 extern "C" int wt_dbg_token_timestamp_postpass(wt_engine* e, int which, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e)) return fail(WT_E_STATE, "wt_dbg_token_timestamp_postpass: mode off");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.tt.n_sel == 0) return fail(WT_E_STATE, "wt_dbg_token_timestamp_postpass: mode off");
     if (which != 1 && which != 2) return fail(WT_E_INVALID, "wt_dbg_token_timestamp_postpass: which = %d", which);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
     TokTsParams p;
     tt_fill(e, p);
-    if (which == 1) for (int b = 0; b < e->B; ++b) LAUNCH(launch_tt_matrix(p, b, s));
+    if (which == 1) for (int b = 0; b < e->cfg.key.B; ++b) LAUNCH(launch_tt_matrix(p, b, s));
     else LAUNCH(launch_tt_dtw(p, s));
     return WT_OK;
 }
@@ -1891,19 +1712,19 @@ extern "C" size_t wt_dbg_token_timestamp_bytes(const wt_engine* e) { return e ? 
 // debug read-backs (whisper_trtllm_amd_debug.h): the captured queries [n_sel][B][max_length - 1][64] and, after
 // wt_decoder_read_token_timestamps, the matrix [B][max_length - 1][S] (rows >= cur_len - 1 are not written)
 extern "C" int wt_dbg_token_timestamp_q_hist(wt_engine* e, float* out, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e)) return fail(WT_E_STATE, "wt_dbg_token_timestamp_q_hist: mode off");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.tt.n_sel == 0) return fail(WT_E_STATE, "wt_dbg_token_timestamp_q_hist: mode off");
     if (!out) return fail(WT_E_INVALID, "wt_dbg_token_timestamp_q_hist: null output");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
-    HIPCHK(hipMemcpyAsync(out, e->tt_qh, (size_t)e->tt_cur.n_sel * e->tt_rows * e->tt_steps * HEAD_DIM * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(out, e->tt_qh, (size_t)e->cfg.key.tt.n_sel * e->cfg.key.tt_rows * e->cfg.key.tt_steps * HEAD_DIM * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 extern "C" int wt_dbg_token_timestamp_matrix(wt_engine* e, float* out, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !tt_on(e)) return fail(WT_E_STATE, "wt_dbg_token_timestamp_matrix: mode off");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.tt.n_sel == 0) return fail(WT_E_STATE, "wt_dbg_token_timestamp_matrix: mode off");
     if (!out) return fail(WT_E_INVALID, "wt_dbg_token_timestamp_matrix: null output");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
-    HIPCHK(hipMemcpyAsync(out, e->tt_matrix, (size_t)e->tt_rows * e->tt_steps * e->S * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(out, e->tt_matrix, (size_t)e->cfg.key.tt_rows * e->cfg.key.tt_steps * e->S * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 // the resident cross-K rows of one (layer, head): [B][S][64] widened to float (fp16 engines keep them in half) -- host staging, synchronises
@@ -1915,7 +1736,7 @@ extern "C" int wt_dbg_cross_k_head(wt_engine* e, int layer, int head, float* out
     const size_t n = (size_t)e->S * HEAD_DIM;
     std::vector<char> tmp(n * e->kv_esz);
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    for (int b = 0; b < e->B; ++b) {
+    for (int b = 0; b < e->cfg.key.B; ++b) {
         const char* src = (const char*)e->cross_k + ((((size_t)layer * e->cross_rows + b) * e->H + head) * n) * e->kv_esz;
         HIPCHK(hipMemcpy(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost));
         if (e->kv_esz == 4) memcpy(out_host + b * n, tmp.data(), n * 4);
@@ -1926,7 +1747,7 @@ extern "C" int wt_dbg_cross_k_head(wt_engine* e, int layer, int head, float* out
 
 // the resident self-K / self-V rows of one (layer, head): [B][T][64] -- host staging, synchronises
 extern "C" int wt_dbg_self_kv_head(wt_engine* e, int layer, int head, int which, float* out_host, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->stream_mode) return fail(WT_E_STATE, "wt_dbg_self_kv_head: no batch decode in flight");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.stream) return fail(WT_E_STATE, "wt_dbg_self_kv_head: no batch decode in flight");
     if (!out_host || layer < 0 || layer >= e->L || head < 0 || head >= e->H || (which != 0 && which != 1))
         return fail(WT_E_INVALID, "wt_dbg_self_kv_head: bad arguments");
     if (e->kv_esz != 4) return fail(WT_E_UNSUPPORTED, "wt_dbg_self_kv_head: fp32 decoder engines only");
@@ -1935,28 +1756,28 @@ extern "C" int wt_dbg_self_kv_head(wt_engine* e, int layer, int head, int which,
     const size_t n = (size_t)e->T * HEAD_DIM;
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     const float* cache = which ? e->self_v : e->self_k;
-    for (int b = 0; b < e->B; ++b)
-        HIPCHK(hipMemcpy(out_host + b * n, cache + (((size_t)layer * e->B + b) * e->H + head) * n, n * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < e->cfg.key.B; ++b)
+        HIPCHK(hipMemcpy(out_host + b * n, cache + (((size_t)layer * e->cfg.key.B + b) * e->H + head) * n, n * 4, hipMemcpyDeviceToHost));
     return WT_OK;
 }
 
 // debug read-back: the plain logits [rows][V] the last executed step of a beam decode left in HBM
 extern "C" int wt_dbg_beam_logits(wt_engine* e, float* logits_out, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !beam_on(e)) return fail(WT_E_STATE, "wt_dbg_beam_logits: no beam decode in flight");
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.beam.num_beams <= 1) return fail(WT_E_STATE, "wt_dbg_beam_logits: no beam decode in flight");
     if (!logits_out) return fail(WT_E_INVALID, "wt_dbg_beam_logits: null output");
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
-    HIPCHK(hipMemcpyAsync(logits_out, e->logits, (size_t)e->B * e->V * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(logits_out, e->logits, (size_t)e->cfg.key.B * e->V * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 
 // debug read-back (whisper_trtllm_amd_debug.h): per executed step and row (token, source beam within the utterance, score bits, utterance done)
 extern "C" int wt_dbg_beam_trace(wt_engine* e, int32_t* trace_out, int steps, void* stream) {
-    if (!e || e->kind != WT_KIND_DECODER || !e->begun || !beam_on(e)) return fail(WT_E_STATE, "wt_dbg_beam_trace: no beam decode in flight");
-    if (!trace_out || steps < 1 || steps > e->max_length - 1) return fail(WT_E_INVALID, "wt_dbg_beam_trace: %d steps outside [1, max_length - 1]", steps);
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.beam.num_beams <= 1) return fail(WT_E_STATE, "wt_dbg_beam_trace: no beam decode in flight");
+    if (!trace_out || steps < 1 || steps > e->cfg.key.max_length - 1) return fail(WT_E_INVALID, "wt_dbg_beam_trace: %d steps outside [1, max_length - 1]", steps);
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
-    HIPCHK(hipMemcpyAsync(trace_out, e->beam_dev.trace, (size_t)steps * e->B * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIPCHK(hipMemcpyAsync(trace_out, e->beam_dev.trace, (size_t)steps * e->cfg.key.B * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WT_OK;
 }
 
@@ -1975,9 +1796,7 @@ extern "C" int wt_decoder_greedy(wt_engine* e, const float* enc_hidden, int B, c
 // ------------------------------------------------------------------------------------------------- Session surface
 extern "C" int wt_engine_infer_shapes(wt_engine* e, const wt_tensor_desc* in, int n_in, wt_tensor_desc* out, int* n_out) {
     if (!e) return fail(WT_E_INVALID, "wt_engine_infer_shapes: null argument");
-    EngineDims dims;
-    dims.kind = e->kind; dims.precision = e->precision; dims.d = e->d; dims.H = e->H; dims.L = e->L; dims.F = e->F;
-    dims.C = e->C; dims.S = e->S; dims.T = e->T; dims.V = e->V;
+    const EngineDims dims = engine_dims(e);
     ShapeState st;
     char msg[400] = "";
     const int rc = infer_shapes(dims, in, n_in, out, n_out, &st, msg, sizeof msg);  // host_logic.cpp
@@ -2036,7 +1855,7 @@ extern "C" int wt_engine_run(wt_engine* e, const wt_binding* in, int n_in, const
     StepIO io;
     io.ids = data; io.ids_ld = 1; io.self_k = nsk; io.self_v = nsv; io.self_cap = cache_len + 1;
     io.cross_k = nck; io.cross_v = ncv; io.cross_rows = 1; io.slot_row = nullptr; io.logits = logits; io.B = 1; io.kv_esz = 4;
-    io.nsplit_self = 1; io.nsplit_cross = pick_splits(1, e->H, S);
+    io.nsplit_self = 1; io.nsplit_cross = pick_splits(1, e->H, S); io.nt = 1;
     io.alive = nullptr;
     io.embed = true;
     io.argmax = nullptr; io.argmax_parts = nullptr;
@@ -2095,12 +1914,8 @@ extern "C" int wt_decoder_time_kernel(wt_engine* e, const char* which, int iters
     DeviceGuard guard(e->device);
     HIPCHK(guard.err);
     hipStream_t s = (hipStream_t)stream;
-    StepIO io;
-    io.ids = e->ids; io.ids_ld = e->max_length; io.self_k = e->self_k; io.self_v = e->self_v; io.self_cap = e->T;
-    io.cross_k = e->cross_k; io.cross_v = e->cross_v; io.cross_rows = e->cross_rows; io.logits = e->logits; io.B = e->B; io.kv_esz = e->kv_esz;
-    io.nsplit_self = e->nsplit_self; io.nsplit_cross = e->nsplit_cross; io.embed = false; io.argmax = nullptr; io.argmax_parts = nullptr;
-    io.alive = nullptr; io.slot_row = nullptr;
-    if (beam_on(e)) { io.slot_row = e->beam_dev.urow; io.anc = e->beam_dev.anc; io.anc_ld = e->beam_dev.anc_ld; io.group = e->beam_group; }   // as the beam step runs them
+    StepIO io = step_io(e, 0);   // variant 0: no `alive`, no stream slot_row (a beam decode keeps its row table, as the beam step runs them)
+    io.qh = nullptr;             // and no query history: this entry point times the launches without those three
     struct ProfilingOff {   // no event records inside the capture; the caller's setting comes back on every exit path
         wt_engine* e; bool was;
         explicit ProfilingOff(wt_engine* e_) : e(e_), was(e_->profiling) { e->profiling = false; }
@@ -2120,6 +1935,8 @@ extern "C" int wt_decoder_time_kernel(wt_engine* e, const char* which, int iters
     }
     return replay_and_time(g, iters, e->L, avg_us, s);
 }
+
+extern "C" int wt_dbg_step_graph_captures(const wt_engine* e) { return e ? e->graph_captures : 0; }
 
 extern "C" int wt_engine_set_profiling(wt_engine* e, int enabled) {
     if (!e) return fail(WT_E_INVALID, "null engine");

@@ -176,4 +176,133 @@ int infer_shapes(const EngineDims& e, const wt_tensor_desc* in, int n_in, wt_ten
     return WT_OK;
 }
 
+// --------------------------------------------------------------------------------------------- decode configuration
+int pick_splits(int B, int H, int len) {
+    // Key splits of the cross-attention launch.  Two splits are merged for free by the consuming GEMV (deferred merge), more
+    // are merged by the attention kernel's last-arriving block, which costs ~2 us: measured on medium.en, ms per step at
+    // B = 1: 16 splits 1.25, 8: 1.12, 4: 1.09, 2: 1.14;  B = 2: 8: 1.16, 4: 1.12, 2: 1.15;  B = 4: 4: 1.27, 2: 1.26;
+    // B = 8: 2: 1.47, 3: 1.76, 4: 1.80.  So: 4 while (utterance, head) pairs are scarce (<= 64), else 2, none from 256 pairs up.
+    int n = (256 + B * H - 1) / (B * H);
+    n = n >= 4 ? 4 : n >= 2 ? 2 : 1;   // (tiny.en B = 8, 48 pairs: 4 splits 0.218, 2 splits 0.225; small.en B = 8, 96 pairs: 2 splits 0.693, 4: 0.706)
+    while (n > 1 && len / n < 48) n >>= 1;
+    return n;
+}
+
+int resolve_decode_config(const EngineDims& e, const DecodeFacts& f, const DecodeRequest& r, const wt_greedy_params* p, int rows, int pool_rows,
+                          bool stream, DecodeConfig* out, char* err, size_t errlen) {
+    if (!p || !out || rows < 1) return fail(err, errlen, WT_E_INVALID, "resolve_decode_config: bad arguments");
+    memset(out, 0, sizeof *out);   // padding included: StepKey compares bytewise
+    StepKey& k = out->key;
+    const char* who = stream ? "wt_decoder_stream_begin" : "wt_decoder_begin";
+    const int nb = !stream && r.beam.num_beams > 1 ? r.beam.num_beams : 1;
+    int B = rows;
+    if (stream) {
+        if (pool_rows <= 0) pool_rows = 4 * rows;     // slots decoding + 3 x slots prepared ahead
+        if (pool_rows < rows + 1 || pool_rows > STREAM_QCAP)
+            return fail(err, errlen, WT_E_INVALID, "wt_decoder_stream_begin: pool of %d rows outside [slots + 1, %d]", pool_rows, STREAM_QCAP);
+        if (r.ts.enabled) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: timestamp mode is a batch-decode feature (wt_decoder_begin)");
+        if (r.beam.num_beams > 1) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: beam search is a batch-decode feature (wt_decoder_begin)");
+        if (r.tt.n_sel > 0) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token-level timestamps are a batch-decode feature (wt_decoder_begin)");
+        if (r.lp.enabled) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token log-probabilities are a batch-decode feature (wt_decoder_begin)");
+        if (r.samp_temp > 0.f) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: temperature sampling is a batch-decode feature (wt_decoder_begin)");
+        if (r.prompt_len > 0) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: decoder prompts are a batch-decode feature (wt_decoder_begin)");
+        if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
+            return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
+    } else {
+        pool_rows = 0;
+        if (nb > 1) {   // beam search: `rows` utterances decode as rows * num_beams rows, [utterance][beam]
+            if (r.ts.enabled) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and timestamp mode cannot be combined");
+            if (r.tt.n_sel > 0)
+                return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token-level timestamps cannot be combined (no beam_indices)");
+            if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
+                return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: logits_trace / force_eos_step(s) are not available with beam search");
+            if (r.lp.enabled)
+                return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and token log-probabilities cannot be combined (wt_decoder_read_beam_scores is the beams' score)");
+            if (r.samp_temp > 0.f)
+                return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: beam search and temperature sampling cannot be combined");
+            if (rows * nb > MAX_ROWS) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", rows, nb, MAX_ROWS);
+            B = rows * nb;
+        }
+        if (r.prompt_len > 0) {
+            if (f.w_half || f.kv_esz != 4)
+                return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: decoder prompts need an fp32 decoder engine (the prefill's GEMMs and attention are fp32)");
+            if (nb > 1) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and beam search cannot be combined");
+            if (r.tt.n_sel > 0)
+                return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and token-level timestamps cannot be combined (their query history is "
+                                                           "indexed by step and sized by the sequence length)");
+            if (r.prompt_rows != 1 && r.prompt_rows < B)
+                return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_prompt gave %d prompt rows for a batch of %d", r.prompt_rows, B);
+            if (r.prompt_len + 2 > p->max_length)
+                return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: %d prompt tokens + the start token + one generated token > max_length %d", r.prompt_len, p->max_length);
+        }
+        if (r.samp_temp > 0.f && r.samp_list && (int)r.samp_seeds.size() < B)
+            return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_sampling gave %d seeds for a batch of %d", (int)r.samp_seeds.size(), B);
+    }
+    if (B > MAX_ROWS) return fail(err, errlen, WT_E_UNSUPPORTED, "%s: batch %d > %d per call; shard the batch", who, B, MAX_ROWS);
+    if (p->max_length < 2 || p->max_length > e.T) return fail(err, errlen, WT_E_INVALID, "max_length %d outside [2, max_target_positions=%d]", p->max_length, e.T);
+    auto tok_ok = [&](int t) { return t >= 0 && t < e.V; };
+    if (!tok_ok(p->decoder_start_token_id) || !tok_ok(p->eos_token_id) || !tok_ok(p->pad_token_id))
+        return fail(err, errlen, WT_E_INVALID, "start/eos/pad token id outside the vocabulary");
+    for (int i = 0; i < p->n_suppress_tokens; ++i)
+        if (!tok_ok(p->suppress_tokens[i])) return fail(err, errlen, WT_E_INVALID, "suppress token %d outside the vocabulary", p->suppress_tokens[i]);
+    for (int i = 0; i < p->n_begin_suppress_tokens; ++i)
+        if (!tok_ok(p->begin_suppress_tokens[i])) return fail(err, errlen, WT_E_INVALID, "begin-suppress token %d outside the vocabulary", p->begin_suppress_tokens[i]);
+    if (r.ts.enabled) k.ts = r.ts;
+    for (int i = 0; i < p->n_forced; ++i) {
+        const int idx = p->forced_decoder_ids[2 * i], tok = p->forced_decoder_ids[2 * i + 1];
+        if (!tok_ok(tok)) return fail(err, errlen, WT_E_INVALID, "forced token %d outside the vocabulary", tok);
+        if (k.ts.enabled && (tok == k.ts.no_timestamps_token_id || idx >= k.ts.begin_index - 1))   // Force and Timestamp must not fight
+            return fail(err, errlen, WT_E_INVALID, "timestamp mode: forced token %d at %d (no <|notimestamps|>, no forced position >= begin_index - 1 = %d)",
+                        tok, idx, k.ts.begin_index - 1);
+        if (nb > 1 && tok == p->eos_token_id)
+            return fail(err, errlen, WT_E_INVALID, "beam search: forced token %d is the EOS token (no beam could continue)", tok);
+    }
+    if (r.tt.n_sel > 0) {   // the query history the cross-attention launches fill: [n_sel][B][max_length - 1][64]
+        if (p->max_length - 1 > TT_MAX_TOKENS) return fail(err, errlen, WT_E_UNSUPPORTED, "token timestamps: %d steps > %d", p->max_length - 1, TT_MAX_TOKENS);
+        k.tt.n_sel = r.tt.n_sel;
+        memcpy(k.tt.layer, r.tt.layer, sizeof k.tt.layer);
+        memcpy(k.tt.head, r.tt.head, sizeof k.tt.head);
+        k.tt_rows = B; k.tt_steps = p->max_length - 1;
+        out->tt_width = r.tt.width; out->tt_time_precision = r.tt.time_precision;
+    }
+    k.B = B; k.max_length = p->max_length; k.begin_index = p->begin_index; k.eos = p->eos_token_id; k.pad = p->pad_token_id;
+    k.start_token = p->decoder_start_token_id; k.force_eos_step = p->force_eos_step; k.force_rows_on = p->force_eos_steps ? 1 : 0;
+    k.logits_trace = p->logits_trace;
+    k.beam = nb > 1 ? r.beam : wt_beam_params{1, 1.f, 0};
+    k.lp = r.lp;
+    k.samp_temp = r.samp_temp > 0.f ? r.samp_temp : 0.f;
+    if (k.samp_temp > 0.f) k.lp.enabled = 1;   // temperature sampling runs the log-probability mode's kernels in their sampling form
+    out->stream = stream; out->pool_rows = pool_rows; out->U = rows;
+    out->prompt_len = r.prompt_len; out->prompt_rows = r.prompt_len > 0 ? (r.prompt_rows == 1 ? 1 : B) : 0;
+    // measured (tools/microbench.py, medium.en B=8): self attention is fastest unsplit at every length <= 448;
+    // cross attention (1500 keys) with ~one block per CU
+    {   // Everything a step touches is read exactly once per step: stream it non-temporally -- unless one whole step (weights + this
+        // batch's K/V) fits the 256 MB Infinity Cache, where default-policy loads let step t+1 hit what step t brought in.
+        // Measured ms per step, non-temporal vs default: tiny.en B=1 (136 MB) 0.171 vs 0.160; tiny.en B=8 (300 MB) 0.224 vs 0.221;
+        // base.en B=8 0.324 vs 0.340; small.en B=8 0.688 vs 0.711; medium.en B=8 1.61 vs 1.66.
+        const double p_step = (double)e.L * (6.0 * e.d * e.d + 2.0 * e.d * e.F) + (double)e.V * e.d;
+        const double step_bytes = (f.w_half ? 2.0 : 4.0) * p_step + (double)B * 2.0 * e.L * e.H * ((double)e.S + p->max_length) * HEAD_DIM * f.kv_esz;
+        k.nt_loads = step_bytes > 160e6;
+    }
+    // self attention: unsplit.  Two key splits with the merge deferred into BOTH halves of the pair launch (WT_NSPLIT_SELF=2) are
+    // implemented and tested, and measured a wash at medium.en batch 8: self-attention 9.0 -> 7.6 us at 447 keys, the pair launch
+    // 8.2 -> 9.7 us (its blocks stage and merge two partial sets), 1.659 vs 1.649 ms per step in one A/B on one box.
+    {
+        const bool can_defer = !f.no_defer_merge && e.d <= 1024;
+        k.nsplit_self = (f.nsplit_self == 2 && can_defer) ? 2 : 1;
+    }
+    {   // beam search: the cross-attention form.  The shared cache rows are read once per beam through slot_row (B blocks per head).  The
+        // grouped form (one block per (utterance, head, split) carrying all beams; num_beams 2 and 4) measured SLOWER at medium.en 4 x 4:
+        // 28.5 against 17.6 us per launch (per-row reading of 16 rows: 32.2), profiles/beam_cost.json -- it is kept as an A/B only:
+        // WT_BEAM_CROSS=grouped (read per decode, so one handle can time both: tools/beam_cost.py).
+        if (f.beam_cross_grouped && (nb == 2 || nb == 4)) k.beam_group = nb;
+        if (nb > 1) k.nsplit_self = 1;   // the ancestry form is unsplit
+    }
+    {
+        const int blocks = k.beam_group > 1 ? B / k.beam_group : B;   // blocks per head and split
+        k.nsplit_cross = f.nsplit_cross_set ? f.nsplit_cross : pick_splits(blocks, e.H, e.S);
+    }
+    return WT_OK;
+}
+
 }  // namespace wt

@@ -7,7 +7,8 @@
 
 #include <atomic>
 
-#include "host_logic.h"  // HEAD_DIM, BlobHeader / BlobTensor, EngineDims (host-only part, also built under ASan/UBSan)
+#include "host_logic.h"  // HEAD_DIM and the decode limits (MAX_ROWS, STREAM_QCAP, MAX_BEAMS, TT_MAX_*), BlobHeader / BlobTensor, EngineDims,
+                         // the decode configuration (host-only part, also built under ASan/UBSan)
 
 namespace wt {
 
@@ -16,8 +17,6 @@ namespace wt {
 // The per-ROW quantities are arrays over the decode slots: a batch started by wt_decoder_begin keeps its rows aligned (all entries
 // equal), the continuous mode (wt_decoder_stream_*) refills a slot with the next waiting utterance the moment its row stops, so every
 // slot runs at its own position -- what the reference's one-clip-at-a-time loop gives for free (run.py:219-226, cal_wer.py:249-287).
-constexpr int MAX_ROWS = 16;       // decode slots per engine call
-constexpr int STREAM_QCAP = 256;   // continuous mode: ring of waiting utterances, and the largest cross-cache pool (rows)
 struct DecState {
     int done;          // stop test fired (all rows EOS, or cur_len >= max_length); continuous mode: no slot active and nothing waiting
     int n_unfinished;  // rows that have not produced EOS yet (continuous mode: active slots)
@@ -188,9 +187,6 @@ hipError_t launch_prefill_state(DecState* st, int* ids, const int* prompt, int n
 // DTW on -matrix with an fp32 cost, cell = (float)((double)(-m) + (double)c), predecessor 0 (diagonal) if c0 < c1 && c0 < c2, else 1 (up)
 // if c1 < c0 && c1 < c2, else 2 (left); backtrace from (N, S) with the borders trace[0][:] = 2, trace[:][0] = 1;
 // out[b][0] = 0, out[b][1 + k] = (float)(time_precision * frame at which the path first reaches token k).
-constexpr int TT_MAX_HEADS = 32;
-constexpr int TT_MAX_WIDTH = 15;
-constexpr int TT_MAX_TOKENS = 1024;   // N of one DTW workgroup (one thread per token row)
 struct TokTsParams {
     const float* q_hist;   // [n_sel][qh_rows][qh_steps][64]
     int qh_rows, qh_steps;
@@ -320,7 +316,6 @@ struct TsPart {
 };
 
 // Beam search (wt_decoder_set_beam_search): rows are [utterance][beam], row = u * nb + j.
-constexpr int MAX_BEAMS = 8;
 constexpr int BEAM_KMAX = 2 * MAX_BEAMS;   // candidates kept per utterance and step: 2 * num_beams
 // One vocabulary chunk of one row (beam_select_kernel -> beam_finish_kernel): the online log-sum-exp pair over ALL ids of the chunk
 // (m = largest non-NaN logit, s = sum of exp(x - m); NaN logits are left out of it) and the chunk's 2 * nb best ids under the
