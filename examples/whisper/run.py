@@ -74,6 +74,11 @@ def parse_arguments():
                         "transcript, shared by every utterance -- token ids, the first of them <|startofprev|> (previous text / "
                         "initial_prompt; text -> ids is the caller's: there is no BPE encoder here); needs a batch plan, an fp32 decoder "
                         "engine, no beams and no --return_token_timestamps")
+    parser.add_argument("--long_form", action="store_true", help="transcribe recordings of any length (--audio files whole, or --synthetic "
+                        "noise recordings of 2.5 windows): openai-whisper's seek loop with the temperature fallback, batched over the files "
+                        "(runtime.transcribe_long); prints [start --> end] text per file; single rank, fp32 decoder engine, no beams")
+    parser.add_argument("--no_condition_on_previous_text", action="store_true", help="--long_form: do not prompt a window with the text before it")
+    parser.add_argument("--max_rows", type=int, default=8, help="--long_form: recordings decoded side by side (<= 16)")
     parser.add_argument("--length_penalty", type=float, default=1.0)
     parser.add_argument("--early_stopping", action="store_true")
     args = parser.parse_args()
@@ -99,6 +104,12 @@ def parse_arguments():
                                         or args.compare or args.engine_precision != "float32"):
         parser.error("--prompt_ids needs the fast path with a batch plan (--batching sorted | dataset) and an fp32 decoder engine: no beams, "
                      "no --return_token_timestamps, no --session / --compare (the Session path takes no prompt)")
+    if args.long_form and (args.session or args.compare or args.num_beams > 1 or args.return_token_timestamps or args.prompt_ids is not None
+                           or args.batching == "continuous" or args.engine_precision != "float32" or args.temperature > 0):
+        parser.error("--long_form runs the batched seek loop on an fp32 decoder engine: no --session / --compare, beams, "
+                     "--return_token_timestamps, --prompt_ids, --temperature (it walks the fallback's list) or --batching continuous")
+    if args.long_form and not 1 <= args.max_rows <= 16:
+        parser.error("--max_rows must be in [1, 16]")
     if args.alignment_heads is not None:
         try:
             args.alignment_heads = [tuple(int(x) for x in pair.split(",")) for pair in args.alignment_heads]
@@ -200,6 +211,46 @@ if __name__ == "__main__":
     if args.max_length:
         config["max_length"] = args.max_length
     name = config.get("name", "whisper-tiny.en")
+    if args.long_form:
+        if world > 1:
+            raise SystemExit("--long_form runs on one rank")
+        window = 2 * config["max_source_positions"]
+        if args.audio:
+            from get_LibriSpeech import read_audio
+            audios = [torch.from_numpy(read_audio(path)).float().cuda() for path in args.audio]
+            names = [os.path.basename(path) for path in args.audio]
+        else:   # noise recordings of 2.5 windows
+            gen = torch.Generator().manual_seed(args.synthetic_start)
+            audios = [(torch.randn(window * tensorrt_llm.audio.HOP * 5 // 2, generator=gen) * 0.1).cuda() for _ in range(args.synthetic)]
+            names = [f"recording {i}" for i in range(args.synthetic)]
+        enc = tensorrt_llm.WhisperEncoderEngine(open(os.path.join(args.engine_dir, "WhisperEncoder.engine"), "rb").read())
+        dec = tensorrt_llm.WhisperDecoderEngine(open(os.path.join(args.engine_dir, "WhisperDecoder.engine"), "rb").read(), config)
+        frontend = tensorrt_llm.audio.LogMelFrontend(n_frames=window)
+        tok = tensorrt_llm.text.WhisperTokenDecoder.from_dir(args.whisper) if os.path.isdir(args.whisper) else None
+        for _ in range(2):  # the first pass is the warm-up, as in run.py:260
+            torch.cuda.synchronize()
+            t0 = time.time()
+            files = tensorrt_llm.runtime.transcribe_long(enc, dec, frontend, audios, condition_on_previous_text=not args.no_condition_on_previous_text,
+                                                         no_speech_token_id=args.no_speech_token_id, max_rows=args.max_rows, seed=args.seed,
+                                                         **({"text_of": lambda ids: tok.decode(ids, skip_special_tokens=True)} if tok else {}))
+            torch.cuda.synchronize()
+            elapsed = time.time() - t0
+        seconds = sum(a.numel() for a in audios) / tensorrt_llm.audio.SAMPLING_RATE
+        print(f"long form   : {elapsed:.3f} s for {seconds:.1f} s of audio in {len(audios)} file(s)  ({seconds / elapsed:.1f} audio-s/s)")
+        tb = tensorrt_llm.runtime.timestamp_rules(config)[1]
+        for fname, segments in zip(names, files):
+            print(f"{fname}:")
+            for seg in segments:
+                if tok:
+                    text = tok.decode_with_timestamps(seg["ids"])
+                else:
+                    text = " ".join(str(t) for t in seg["ids"] if t < tb)
+                print(f"  [{seg['start']:7.2f} --> {seg['end']:7.2f}] {text}")
+        if args.dump_ids:
+            import json
+            json.dump([[dict(start=s["start"], end=s["end"], ids=s["ids"], temperature=s["temperature"], seek=s["seek"]) for s in segs] for segs in files],
+                      open(args.dump_ids, "w"))
+        raise SystemExit(0)
     if args.audio:
         import numpy as np
         from get_LibriSpeech import N_SAMPLES, read_audio

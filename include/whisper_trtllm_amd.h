@@ -316,6 +316,20 @@ typedef struct {
     int32_t len;          /* tokens placed BEFORE decoder_start_token_id, 0 < len */
 } wt_prompt_params;
 int wt_decoder_set_prompt(wt_engine* dec, const wt_prompt_params* p);   /* NULL or len <= 0: off */
+/* (9h) per-row prompt lengths (several recordings under condition_on_previous_text carry different amounts of previous text): row b
+ * holds lens[b] prompt tokens, 0 <= lens[b] <= ld.  With Lmax = the longest row of the decode's batch, row b of the id buffer starts as
+ * pad_token_id x (Lmax - lens[b]), prompt[b][0..lens[b]), decoder_start_token_id -- left-padded, as transformers pads decoder_input_ids
+ * -- and the decode begins at cur_len = Lmax + 1 for EVERY row, so all of (9g)'s absolute positions are shifted by Lmax and max_length
+ * counts Lmax; the row's decoder position and the valid keys of its self cache are its own lens[b] (a row with lens[b] == 0 starts at
+ * position 0 as an unprompted row does), and sampling (9f) draws at the row's own position lens[b] + 1 + generated tokens, so a row's
+ * draws do not depend on its neighbours' prompts.  The prefill runs once over batch x Lmax positions with the rows right-padded;
+ * causality keeps the filler from every real position, and each decode step overwrites its cache row before attention reads it.
+ * wt_decoder_read_ids returns the left-padded rows; the log-probability entries (9e) of positions 0..Lmax are 0.
+ * ids host row-major [n_rows][ld], lens[n_rows] in [0, ld]; copied by the call.  n_rows >= the next decode's
+ * batch.  max(lens) == 0 or ids == NULL: off.  Same refusals as wt_decoder_set_prompt (fp16 decoder engine, beams, token-level
+ * timestamps, the continuous mode); wt_decoder_set_prompt and this call replace each other.  With every lens[b] equal the decode is
+ * bitwise the one wt_decoder_set_prompt gives. */
+int wt_decoder_set_prompt_rows(wt_engine* dec, const int32_t* ids, int n_rows, int ld, const int32_t* lens);
 
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
@@ -378,6 +392,12 @@ void wt_logmel_destroy(wt_logmel* h);
  * untouched.  Samples are expected within |x| <= 32768 (int16 range): beyond it the float32 power spectrum can overflow where the
  * reference's float64 one does not. */
 int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, int n_in, float* mel_out, void* stream);
+/* window b = samples [offsets[b], offsets[b] + n_valid[b]) of the flat device buffer `audio`, zero-padded to the handle's window and
+ * reflected at the WINDOW's edges (not into neighbouring audio); offsets / n_valid: host arrays of `batch` entries, copied by the call.
+ * Bitwise the result of wt_logmel_forward on a copy of that slice.  n_valid[b] >= 1 (longer than the window = trimmed), offsets[b] >= 0;
+ * every window is normalised on its own.  The caller guarantees that the slices lie inside the buffer. */
+int wt_logmel_forward_windows(wt_logmel* h, const float* audio, const int64_t* offsets, const int32_t* n_valid, int batch,
+                              float* mel_out, void* stream);
 
 const char* wt_last_error(void);
 int wt_abi_version(void);

@@ -7,12 +7,12 @@ Mirrors the slice of the `tensorrt_llm` package that examples/whisper uses
 library or without a GPU raises.
 """
 from . import _dtypes as trt  # noqa: F401  `trt.float32` spelling used by the reference's run.py
-from . import audio, builder, convert, engine_pack, english, generation, layers, models, module, network, runtime, sharding, synthetic, text  # noqa: F401
+from . import audio, builder, convert, engine_pack, english, generation, layers, longform, models, module, network, runtime, sharding, synthetic, text  # noqa: F401
 from .builder import Builder, BuilderConfig  # noqa: F401
 from .logger import logger  # noqa: F401
 from .models import WhisperDecoder, WhisperEncoder  # noqa: F401
 from .network import net_guard  # noqa: F401
-from .runtime import DecodeScores, DecodeStream, Session, TensorInfo, WhisperDecoderEngine, WhisperEncoderEngine, WhisperPipeline, transcribe_continuous  # noqa: F401
+from .runtime import DecodeScores, DecodeStream, Session, TensorInfo, WhisperDecoderEngine, WhisperEncoderEngine, WhisperPipeline, transcribe_continuous, transcribe_long  # noqa: F401
 
 __version__ = "0.1.0"
 

@@ -18,9 +18,9 @@ EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
     "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores",
-    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_set_sampling", "wt_decoder_set_prompt", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_set_sampling", "wt_decoder_set_prompt", "wt_decoder_set_prompt_rows", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
-    "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_last_error", "wt_abi_version",
+    "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_logmel_forward_windows", "wt_last_error", "wt_abi_version",
 ]
 DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_gemm_f16", "wt_dbg_gemm_f16_variant", "wt_dbg_layernorm", "wt_dbg_encoder_attention", "wt_dbg_encoder_attention_split", "wt_dbg_encoder_attention_x3", "wt_dbg_encoder_attention_f16", "wt_dbg_skinny", "wt_dbg_skinny_gelu_in", "wt_dbg_encoder_attention_occupancy", "wt_dbg_decode_attention",
                  "wt_dbg_decode_attention_folded", "wt_dbg_skinny_pair", "wt_dbg_attention_then_projection", "wt_dbg_self_attention_then_pair",
@@ -143,6 +143,7 @@ def load():
     lib.wt_decoder_read_logprobs.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.wt_decoder_set_sampling.argtypes = [c_void_p, POINTER(SamplingParams)]
     lib.wt_decoder_set_prompt.argtypes = [c_void_p, POINTER(PromptParams)]
+    lib.wt_decoder_set_prompt_rows.argtypes = [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_int32)]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -153,6 +154,7 @@ def load():
     lib.wt_logmel_destroy.argtypes = [c_void_p]
     lib.wt_logmel_destroy.restype = None
     lib.wt_logmel_forward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
+    lib.wt_logmel_forward_windows.argtypes = [c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int32), c_int, c_void_p, c_void_p]
     lib.wt_decoder_time_cross_attention.argtypes = [c_void_p, c_int, POINTER(c_float), c_void_p]
     lib.wt_decoder_time_kernel.argtypes = [c_void_p, c_char_p, c_int, POINTER(c_float), c_void_p]
     P, I, F = c_void_p, c_int, c_float

@@ -75,9 +75,10 @@ def valid_frames(mel) -> list:
 
 
 class LogMelFrontend:
-    """waveforms float32 [B, n] on the GPU (16 kHz mono) -> log-mel float32 [B, 80, 3000]; asynchronous."""
+    """waveforms float32 [B, n] on the GPU (16 kHz mono) -> log-mel float32 [B, 80, n_frames]; asynchronous.  `n_frames`: the window in
+    frames (default: Whisper's 3000 = 30 s; a toy model's encoder takes 2 * max_source_positions)."""
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, n_frames: int = N_FRAMES):
         import torch
         self._lib = _lib.load()
         if not torch.cuda.is_available():
@@ -89,7 +90,8 @@ class LogMelFrontend:
         filt[:, :n_bins] = mel_filter_bank().T.astype(np.float32)
         win = np.ascontiguousarray(hann_window(), dtype=np.float64)   # the reference frames in float64 (audio_utils.py:399-401)
         self._handle = ctypes.c_void_p()
-        _lib.check(self._lib.wt_logmel_create(dev, N_FFT, HOP, N_MELS, N_FRAMES, win.ctypes.data, filt.ctypes.data, npw,
+        self.n_frames = int(n_frames)
+        _lib.check(self._lib.wt_logmel_create(dev, N_FFT, HOP, N_MELS, self.n_frames, win.ctypes.data, filt.ctypes.data, npw,
                                               ctypes.byref(self._handle)), "wt_logmel_create")
 
     def __call__(self, waveforms):
@@ -99,10 +101,33 @@ class LogMelFrontend:
         if waveforms.dtype != torch.float32 or not waveforms.is_cuda:
             raise ValueError("waveforms must be a float32 CUDA tensor [B, n_samples]")
         w = waveforms.contiguous()
-        out = torch.empty(w.shape[0], N_MELS, N_FRAMES, dtype=torch.float32, device=w.device)
+        out = torch.empty(w.shape[0], N_MELS, self.n_frames, dtype=torch.float32, device=w.device)
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_logmel_forward(self._handle, w.data_ptr(), w.shape[0], w.shape[1], out.data_ptr(),
                                                ctypes.c_void_p(stream)), "wt_logmel_forward")
+        return out
+
+    def windows(self, audio_flat, offsets, n_valid):
+        """Windows inside one flat buffer (wt_logmel_forward_windows): window b = samples [offsets[b], offsets[b] + n_valid[b]) of the 1-D
+        float32 GPU tensor `audio_flat`, zero-padded to the window and reflected at its own edges -> float32 [len(offsets), 80, n_frames],
+        bitwise what __call__ gives on a copy of each slice; every window is normalised on its own.  No padded copies are made."""
+        import torch
+        if audio_flat.dim() != 1 or audio_flat.dtype != torch.float32 or not audio_flat.is_cuda:
+            raise ValueError("audio_flat must be a 1-D float32 CUDA tensor")
+        offsets, n_valid = [int(o) for o in offsets], [int(n) for n in n_valid]
+        if not offsets or len(offsets) != len(n_valid):
+            raise ValueError("offsets and n_valid need one entry per window (at least one)")
+        for o, n in zip(offsets, n_valid):   # nothing outside the buffer may be read
+            if o < 0 or n < 1 or o + n > audio_flat.numel():
+                raise ValueError(f"window [{o}, {o} + {n}) lies outside the buffer of {audio_flat.numel()} samples")
+        w = audio_flat.contiguous()
+        nw = len(offsets)
+        out = torch.empty(nw, N_MELS, self.n_frames, dtype=torch.float32, device=w.device)
+        off = (ctypes.c_int64 * nw)(*offsets)
+        val = (ctypes.c_int32 * nw)(*n_valid)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self._lib.wt_logmel_forward_windows(self._handle, w.data_ptr(), off, val, nw, out.data_ptr(), ctypes.c_void_p(stream)),
+                   "wt_logmel_forward_windows")
         return out
 
     def __del__(self):

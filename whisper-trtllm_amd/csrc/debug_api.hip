@@ -645,9 +645,10 @@ extern "C" int wt_dbg_greedy_select(const float* logits, const float* part_val, 
     if (fused ? (!part_val || !part_idx || n_parts < 1) : (part_val || part_idx)) return -22;
     if (eos < 0 || eos >= V || pad < 0 || pad >= V) return -22;
     if (next_x && (!tok_emb || !pos_emb || d < 4 || (d & 3))) return -22;
-    for (int b = 0; b < B; ++b)   // greedy_select_kernel reads cur_len[b]; greedy_finish_kernel indexes ids / forced / pos_emb by row 0's counters
+    for (int b = 0; b < B; ++b)   // greedy_select_kernel reads cur_len[b]; greedy_finish_kernel indexes ids / forced by row 0's cur_len
         if (state[4 + b] < 1 || state[4 + b] >= max_length) return -22;
-    if (next_x && (state[4 + MAX_ROWS] < -1 || state[4 + MAX_ROWS] + 1 >= pos_rows)) return -22;
+    for (int b = 0; b < B; ++b)   // ... and advances pos / self_len per row: every row's next position must lie inside pos_emb
+        if (next_x && (state[4 + MAX_ROWS + b] < -1 || state[4 + MAX_ROWS + b] + 1 >= pos_rows)) return -22;
     for (int i = 0; i < max_length; ++i)
         if (forced[i] >= V) return -22;
     hipStream_t s = (hipStream_t)stream;

@@ -164,6 +164,7 @@ struct wt_engine {
     int* tt_sel = nullptr;        // device [L][H]: selection index of (layer, head), or -1
     uint8_t* tt_trace = nullptr;
     std::vector<int> tt_h_sel;    // host image of tt_sel
+    std::vector<int> h_prompt;    // ragged decoder prompt: the right-padded id matrix + lengths of the decode in flight (source of an async copy)
     char* pf_ws = nullptr;        // decoder prompt: the prefill's workspace (allocated by the first prompt decode, grown when needed)
     size_t pf_bytes = 0;
     hipStream_t own_stream = nullptr;
@@ -1124,6 +1125,7 @@ extern "C" int wt_decoder_set_prompt(wt_engine* e, const wt_prompt_params* p) {
     if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_prompt: not a decoder engine");
     if (!p || p->len <= 0) {
         e->req.prompt.clear();
+        e->req.prompt_lens.clear();
         e->req.prompt_rows = e->req.prompt_len = 0;
         return WT_OK;
     }
@@ -1136,6 +1138,37 @@ extern "C" int wt_decoder_set_prompt(wt_engine* e, const wt_prompt_params* p) {
     e->req.prompt.assign(p->ids, p->ids + n);
     e->req.prompt_rows = p->n_rows;
     e->req.prompt_len = p->len;
+    e->req.prompt_lens.clear();
+    return WT_OK;
+}
+
+extern "C" int wt_decoder_set_prompt_rows(wt_engine* e, const int32_t* ids, int n_rows, int ld, const int32_t* lens) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_prompt_rows: not a decoder engine");
+    int lmax = 0;
+    if (ids && lens) {
+        if (n_rows < 1 || ld < 1) return fail(WT_E_INVALID, "wt_decoder_set_prompt_rows: %d rows of leading dimension %d", n_rows, ld);
+        for (int b = 0; b < n_rows; ++b) {
+            if (lens[b] < 0 || lens[b] > ld) return fail(WT_E_INVALID, "wt_decoder_set_prompt_rows: row %d holds %d tokens, outside [0, %d]", b, lens[b], ld);
+            lmax = lens[b] > lmax ? lens[b] : lmax;
+        }
+    }
+    if (lmax == 0) {
+        e->req.prompt.clear();
+        e->req.prompt_lens.clear();
+        e->req.prompt_rows = e->req.prompt_len = 0;
+        return WT_OK;
+    }
+    if (lmax >= e->T) return fail(WT_E_INVALID, "wt_decoder_set_prompt_rows: %d prompt tokens >= max_target_positions %d", lmax, e->T);
+    for (int b = 0; b < n_rows; ++b)
+        for (int j = 0; j < lens[b]; ++j) {
+            const int tok = ids[(size_t)b * ld + j];
+            if (tok < 0 || tok >= e->V) return fail(WT_E_INVALID, "wt_decoder_set_prompt_rows: token %d (row %d, position %d) outside the vocabulary", tok, b, j);
+        }
+    e->req.prompt.assign((size_t)n_rows * lmax, 0);   // [n_rows][lmax]; what lies behind a row's tokens is never read
+    for (int b = 0; b < n_rows; ++b) memcpy(e->req.prompt.data() + (size_t)b * lmax, ids + (size_t)b * ld, (size_t)lens[b] * 4);
+    e->req.prompt_lens.assign(lens, lens + n_rows);
+    e->req.prompt_rows = n_rows;
+    e->req.prompt_len = lmax;
     return WT_OK;
 }
 
@@ -1149,7 +1182,7 @@ static int prefill_reserve(wt_engine* e, int B, int len, hipStream_t s, float** 
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
     // h, h1, x, q: [M][d]; ah: [M][2d] (self-attention context | layer input); ffn: [M][F]; the prompt ids
     const size_t o_h = take(M * d * 4), o_h1 = take(M * d * 4), o_x = take(M * d * 4), o_q = take(M * d * 4), o_ah = take(M * 2 * d * 4);
-    const size_t o_f = take(M * e->F * 4), o_ids = take((size_t)MAX_ROWS * e->T * 4);
+    const size_t o_f = take(M * e->F * 4), o_ids = take(((size_t)MAX_ROWS * e->T + MAX_ROWS) * 4);   // (+ the per-row lengths of the ragged form)
     if (off > e->pf_bytes) {
         HIPCHK(hipStreamSynchronize(s));   // nothing of an earlier decode may still use the old buffer
         if (e->pf_ws) { hipFree(e->pf_ws); e->pf_ws = nullptr; e->pf_bytes = 0; }
@@ -1250,8 +1283,18 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
         rc = prefill_reserve(e, B, plen, s, pf_bufs, &pf_ids);
         if (rc) return rc;
         // (pageable source kept alive by the handle, as the sampling seeds above)
-        HIPCHK(hipMemcpyAsync(pf_ids, e->req.prompt.data(), (size_t)c.prompt_rows * plen * 4, hipMemcpyHostToDevice, s));
-        LAUNCH(launch_prefill_state(e->st, e->ids, pf_ids, c.prompt_rows, plen, B, k.max_length, k.start_token, s));
+        if (c.prompt_ragged) {   // the pass's own id matrix [B][plen]: the rows' tokens, right-padded with the pad id; the lengths ride behind it
+            e->h_prompt.assign((size_t)B * plen + MAX_ROWS, k.pad);
+            for (int b = 0; b < B; ++b) {
+                memcpy(e->h_prompt.data() + (size_t)b * plen, e->req.prompt.data() + (size_t)b * e->req.prompt_len, (size_t)c.prompt_lens[b] * 4);
+                e->h_prompt[(size_t)B * plen + b] = c.prompt_lens[b];
+            }
+            HIPCHK(hipMemcpyAsync(pf_ids, e->h_prompt.data(), ((size_t)B * plen + MAX_ROWS) * 4, hipMemcpyHostToDevice, s));
+            LAUNCH(launch_prefill_state_rows(e->st, e->ids, pf_ids, pf_ids + (size_t)B * plen, plen, B, k.max_length, k.start_token, k.pad, s));
+        } else {
+            HIPCHK(hipMemcpyAsync(pf_ids, e->req.prompt.data(), (size_t)c.prompt_rows * plen * 4, hipMemcpyHostToDevice, s));
+            LAUNCH(launch_prefill_state(e->st, e->ids, pf_ids, c.prompt_rows, plen, B, k.max_length, k.start_token, s));
+        }
     }
     LAUNCH(launch_dec_embed(e->ids, k.max_length, e->tok_emb, e->pos_emb, e->dh, B, e->d, e->st, s, e->w_half));  // input of step 0
     // the beams of an utterance attend over the same encoder memory: its cross K/V are projected once, into cache row u

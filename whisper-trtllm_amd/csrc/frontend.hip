@@ -44,17 +44,27 @@ typedef double d4v __attribute__((ext_vector_type(4)));
 constexpr int DFT_FRAMES = 64;       // frames per workgroup
 constexpr int DFT_MAX_BT = 7;        // bin tiles per wave half (n_fft <= 446)
 
+// Windowed form (wt_logmel_forward_windows): row b0 + blockIdx.y reads rows.valid[blockIdx.y] samples from audio + rows.base[blockIdx.y] instead
+// of n_in samples from audio + b * n_in.  The reflect indices stay relative to the window, and nothing outside [base, base + valid) is read.
+constexpr int DFT_ROWS = 16;         // windows per launch of the windowed form (their bases and lengths travel as kernel arguments)
+struct DftRows {
+    long long base[DFT_ROWS];
+    int valid[DFT_ROWS];
+};
+
 __global__ __launch_bounds__(256) void dft_power_f64_kernel(const float* __restrict__ audio, int n_in, int n_samples,
                                                             const double* __restrict__ window, const double* __restrict__ frag,
-                                                            float* __restrict__ pw, int T, int n_fft, int hop, int npw, int nbt) {
+                                                            float* __restrict__ pw, int T, int n_fft, int hop, int npw, int nbt,
+                                                            const DftRows rows, const int windowed, const int b0) {
     extern __shared__ __attribute__((aligned(16))) double dft_smem[];
     double* s_w = dft_smem;                                        // [n_fft]
     float* s_x = reinterpret_cast<float*>(dft_smem + n_fft);       // [(DFT_FRAMES - 1) * hop + n_fft]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fg = wave & 1, half = wave >> 1;
-    const int b = blockIdx.y, t0 = blockIdx.x * DFT_FRAMES;
+    const int b = b0 + blockIdx.y, t0 = blockIdx.x * DFT_FRAMES;
     const int span = (DFT_FRAMES - 1) * hop + n_fft, ksteps = n_fft >> 2;
-    const float* x = audio + (size_t)b * n_in;
+    const float* x = windowed ? audio + rows.base[blockIdx.y] : audio + (size_t)b * n_in;
+    if (windowed) n_in = rows.valid[blockIdx.y];
     for (int i = tid; i < span; i += 256) {
         long long sidx = (long long)t0 * hop + i - n_fft / 2;     // index into the 30 s signal
         if (sidx < 0) sidx = -sidx;                               // np.pad(mode="reflect")
@@ -230,8 +240,9 @@ extern "C" void wt_logmel_destroy(wt_logmel* h) {
     delete h;
 }
 
-extern "C" int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, int n_in, float* mel_out, void* stream) {
-    if (!h || !audio || !mel_out || batch < 1 || n_in < 1) return wt_set_error(WT_E_INVALID, "wt_logmel_forward: bad arguments");
+// offsets / n_valid (host, `batch` entries): the windowed form; both null: row b = n_in samples at audio + b * n_in
+static int logmel_run(wt_logmel* h, const float* audio, int batch, int n_in, const int64_t* offsets, const int32_t* n_valid, float* mel_out,
+                      void* stream) {
     wt::DeviceGuard guard(h->device);
     if (guard.err != hipSuccess) return wt_set_error(WT_E_HIP, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
@@ -250,8 +261,22 @@ extern "C" int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, in
         h->cap = batch;
     }
     const int smem = h->n_fft * 8 + ((DFT_FRAMES - 1) * h->hop + h->n_fft) * 4;
-    hipLaunchKernelGGL(dft_power_f64_kernel, dim3((T + DFT_FRAMES - 1) / DFT_FRAMES, batch), dim3(256), smem, s, audio, n_in, h->n_samples,
-                       h->window, h->frag, h->pw, T, h->n_fft, h->hop, h->npw, h->nbt);
+    DftRows rows;
+    memset(&rows, 0, sizeof rows);
+    if (!offsets) {
+        hipLaunchKernelGGL(dft_power_f64_kernel, dim3((T + DFT_FRAMES - 1) / DFT_FRAMES, batch), dim3(256), smem, s, audio, n_in, h->n_samples,
+                           h->window, h->frag, h->pw, T, h->n_fft, h->hop, h->npw, h->nbt, rows, 0, 0);
+    } else {
+        for (int b0 = 0; b0 < batch; b0 += DFT_ROWS) {
+            const int nb = batch - b0 < DFT_ROWS ? batch - b0 : DFT_ROWS;
+            for (int i = 0; i < nb; ++i) {
+                rows.base[i] = offsets[b0 + i];
+                rows.valid[i] = n_valid[b0 + i];
+            }
+            hipLaunchKernelGGL(dft_power_f64_kernel, dim3((T + DFT_FRAMES - 1) / DFT_FRAMES, nb), dim3(256), smem, s, audio, 0, h->n_samples,
+                               h->window, h->frag, h->pw, T, h->n_fft, h->hop, h->npw, h->nbt, rows, 1, b0);
+        }
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wt_set_error(WT_E_HIP, "DFT kernel launch failed: %s", hipGetErrorString(e));
     // mel projection: 201-term sums of non-negative products -- no cancellation, the fp32 MFMA GEMM is within 1e-6 relative
@@ -266,6 +291,20 @@ extern "C" int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, in
     e = hipGetLastError();
     if (e != hipSuccess) return wt_set_error(WT_E_HIP, "front-end kernel launch failed: %s", hipGetErrorString(e));
     return WT_OK;
+}
+
+extern "C" int wt_logmel_forward(wt_logmel* h, const float* audio, int batch, int n_in, float* mel_out, void* stream) {
+    if (!h || !audio || !mel_out || batch < 1 || n_in < 1) return wt_set_error(WT_E_INVALID, "wt_logmel_forward: bad arguments");
+    return logmel_run(h, audio, batch, n_in, nullptr, nullptr, mel_out, stream);
+}
+
+extern "C" int wt_logmel_forward_windows(wt_logmel* h, const float* audio, const int64_t* offsets, const int32_t* n_valid, int batch,
+                                         float* mel_out, void* stream) {
+    if (!h || !audio || !offsets || !n_valid || !mel_out || batch < 1) return wt_set_error(WT_E_INVALID, "wt_logmel_forward_windows: bad arguments");
+    for (int b = 0; b < batch; ++b)
+        if (offsets[b] < 0 || n_valid[b] < 1)
+            return wt_set_error(WT_E_INVALID, "wt_logmel_forward_windows: window %d starts at %lld with %d samples", b, (long long)offsets[b], n_valid[b]);
+    return logmel_run(h, audio, batch, 0, offsets, n_valid, mel_out, stream);
 }
 
 // test hook (whisper_trtllm_amd_debug.h): the intermediate buffers of the last wt_logmel_forward of `batch` utterances

@@ -223,17 +223,33 @@ int resolve_decode_config(const EngineDims& e, const DecodeFacts& f, const Decod
             if (rows * nb > MAX_ROWS) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: %d utterances x %d beams > %d rows per call", rows, nb, MAX_ROWS);
             B = rows * nb;
         }
-        if (r.prompt_len > 0) {
+        // per-row lengths: the batch's longest row is the prompt length every batch-wide rule counts with (0: no row of this batch has a prompt)
+        int plen = r.prompt_len;
+        const bool ragged = plen > 0 && !r.prompt_lens.empty();
+        if (ragged) {   // (too few rows for the batch: refused below, behind the combinations that are refused whatever the rows)
+            plen = 0;
+            for (int b = 0; b < B && b < (int)r.prompt_lens.size(); ++b) plen = r.prompt_lens[b] > plen ? r.prompt_lens[b] : plen;
+            if ((int)r.prompt_lens.size() < B) plen = r.prompt_len;
+        }
+        out->prompt_len = plen;
+        if (plen > 0) {
             if (f.w_half || f.kv_esz != 4)
                 return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: decoder prompts need an fp32 decoder engine (the prefill's GEMMs and attention are fp32)");
             if (nb > 1) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and beam search cannot be combined");
             if (r.tt.n_sel > 0)
                 return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: a decoder prompt and token-level timestamps cannot be combined (their query history is "
                                                            "indexed by step and sized by the sequence length)");
+            if (ragged && (r.prompt_rows < B || (int)r.prompt_lens.size() < B))
+                return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_prompt_rows gave %d prompt rows for a batch of %d", r.prompt_rows, B);
             if (r.prompt_rows != 1 && r.prompt_rows < B)
                 return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_prompt gave %d prompt rows for a batch of %d", r.prompt_rows, B);
-            if (r.prompt_len + 2 > p->max_length)
-                return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: %d prompt tokens + the start token + one generated token > max_length %d", r.prompt_len, p->max_length);
+            if (plen + 2 > p->max_length)
+                return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: %d prompt tokens + the start token + one generated token > max_length %d", plen, p->max_length);
+            out->prompt_rows = r.prompt_rows == 1 ? 1 : B;
+            if (ragged) {
+                out->prompt_ragged = 1;
+                for (int b = 0; b < B; ++b) out->prompt_lens[b] = r.prompt_lens[b];
+            }
         }
         if (r.samp_temp > 0.f && r.samp_list && (int)r.samp_seeds.size() < B)
             return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_sampling gave %d seeds for a batch of %d", (int)r.samp_seeds.size(), B);
@@ -273,7 +289,6 @@ int resolve_decode_config(const EngineDims& e, const DecodeFacts& f, const Decod
     k.samp_temp = r.samp_temp > 0.f ? r.samp_temp : 0.f;
     if (k.samp_temp > 0.f) k.lp.enabled = 1;   // temperature sampling runs the log-probability mode's kernels in their sampling form
     out->stream = stream; out->pool_rows = pool_rows; out->U = rows;
-    out->prompt_len = r.prompt_len; out->prompt_rows = r.prompt_len > 0 ? (r.prompt_rows == 1 ? 1 : B) : 0;
     // measured (tools/microbench.py, medium.en B=8): self attention is fastest unsplit at every length <= 448;
     // cross attention (1500 keys) with ~one block per CU
     {   // Everything a step touches is read exactly once per step: stream it non-temporally -- unless one whole step (weights + this

@@ -80,6 +80,7 @@ struct DecodeRequest {
     } tt;
     std::vector<int> prompt;                    // [prompt_rows][prompt_len]; len 0: off
     int prompt_rows = 0, prompt_len = 0;
+    std::vector<int> prompt_lens;               // wt_decoder_set_prompt_rows: tokens of each row of `prompt` ([prompt_rows][prompt_len]); empty: every row holds prompt_len
 };
 
 // Exactly the values a captured step graph bakes into kernel arguments: the graphs are replayed while the key of the decode in flight
@@ -118,6 +119,8 @@ struct DecodeConfig {
     int pool_rows;             // 0 in a batch decode
     int U;                     // utterances: key.B = U * num_beams
     int prompt_len, prompt_rows;   // decoder prompt: tokens in front of the start token (0: off) and the rows uploaded (1: shared, or B)
+    int prompt_ragged;             // per-row prompt lengths (wt_decoder_set_prompt_rows): prompt_len is then the longest of the batch's rows, ...
+    int prompt_lens[MAX_ROWS];     // ... these are the rows' own, and the id rows are left-padded to prompt_len
     int tt_width;              // token timestamps: median filter width and seconds per encoder frame
     double tt_time_precision;
 };

@@ -361,7 +361,7 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int nsp
     int sm_t = 0;
     if constexpr (SAMP) {
         sm_seed = p.am_seeds[min(my_b, p.B - 1)];
-        sm_t = p.st->cur_len[min(my_b, p.B - 1)];
+        sm_t = p.st->pos[min(my_b, p.B - 1)] + 1;   // the row's own sequence position (== cur_len unless the id rows are left-padded)
     }
     if constexpr (ARGMAX) {
         am_mk[0] = p.am_mask[min(row_begin + my_r, p.N - 1)];
@@ -1322,6 +1322,7 @@ __global__ __launch_bounds__(64) void sample_select_kernel(const SelectParams p,
     const DecState* st = p.st;
     if (st->done) return;  // steps enqueued past the stop test are no-ops
     const int tid = threadIdx.x, block = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
+    const int samp_t = st->pos[b] + 1;   // the draws' position is the row's own (== cur_len unless the id rows are left-padded)
     const bool at_begin = cur_len == p.begin_index;
     const float* lg = p.logits + (size_t)b * p.V;
     float* tr = p.trace ? p.trace + ((size_t)b * (p.max_length - 1) + step) * p.V : nullptr;
@@ -1344,7 +1345,7 @@ __global__ __launch_bounds__(64) void sample_select_kernel(const SelectParams p,
             lse_add(lm, ls, x);
             if (n == p.eos) p.lp_side[2 * b] = x;
             unsigned dr[4];
-            sample_draws(seed, cur_len, n >> 2, dr);
+            sample_draws(seed, samp_t, n >> 2, dr);
             const int q = n & 3;
             const float key = sample_key(x, p.samp_temp, q == 0 ? dr[0] : q == 1 ? dr[1] : q == 2 ? dr[2] : dr[3]);
             if (argmax_better(key, n, best, bidx)) {
@@ -1399,6 +1400,7 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
     const DecState* st = p.st;
     if (st->done) return;  // steps enqueued past the stop test are no-ops
     const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y, cur_len = st->cur_len[b], step = st->step;
+    [[maybe_unused]] const int samp_t = st->pos[b] + 1;   // SAMP: the draws' position is the row's own (== cur_len unless the id rows are left-padded)
     const bool at_begin = cur_len == p.begin_index;
     const float* lg = p.logits + (size_t)b * p.V;
     float* tr = p.trace ? p.trace + ((size_t)b * (p.max_length - 1) + step) * p.V : nullptr;
@@ -1476,7 +1478,7 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
             const uchar4 m = mk4[i];
             if (tr) tr4[i] = x;
             unsigned dr[4] = {0u, 0u, 0u, 0u};
-            if constexpr (SAMP) sample_draws(seed, cur_len, i, dr);
+            if constexpr (SAMP) sample_draws(seed, samp_t, i, dr);
             consider(x.x, m.x, 4 * i, dr[0]);
             consider(x.y, m.y, 4 * i + 1, dr[1]);
             consider(x.z, m.z, 4 * i + 2, dr[2]);
@@ -1489,7 +1491,7 @@ __global__ __launch_bounds__(256) void ts_select_kernel(const SelectParams p) {
             const float x = lg[v];
             if (tr) tr[v] = x;
             unsigned dr[4] = {0u, 0u, 0u, 0u};
-            if constexpr (SAMP) sample_draws(seed, cur_len, v >> 2, dr);
+            if constexpr (SAMP) sample_draws(seed, samp_t, v >> 2, dr);
             const int k = v & 3;
             consider(x, p.mask[v], v, k == 0 ? dr[0] : k == 1 ? dr[1] : k == 2 ? dr[2] : dr[3]);
         }
@@ -1755,9 +1757,10 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
         finish_request(p, b, l, lpb, cand);
     }
     const int unf = p.unfinished[bc];
-    // the rows of a wt_decoder_begin batch stay aligned: row 0's counters are everybody's
-    const int done = st->done, cur_len = st->cur_len[0], step = st->step, pos = st->pos[0], self_len = st->self_len[0], seq = st->seq + 1,
-              epoch = st->epoch;
+    // the rows of a wt_decoder_begin batch stay aligned in the id buffer: row 0's cur_len is everybody's.  The decoder position and the
+    // self cache's key count are the row's own (they differ between rows behind prompts of unequal lengths, whose id rows are left-padded)
+    const int done = st->done, cur_len = st->cur_len[0], step = st->step, seq = st->seq + 1, epoch = st->epoch;
+    const int pos = st->pos[bc], my_pos = st->pos[min(tid, p.B - 1)], my_self_len = st->self_len[min(tid, p.B - 1)];
     if (done) {         // block-uniform: steps enqueued past the stop test are no-ops (the host still sees them retire)
         if (tid == 0) {
             st->seq = seq;
@@ -1821,8 +1824,8 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     __syncthreads();   // (every thread has read the counters above before any of them is advanced)
     if (tid < p.B) {
         st->cur_len[tid] = cur_len + 1;
-        st->pos[tid] = pos + 1;
-        st->self_len[tid] = self_len + 1;
+        st->pos[tid] = my_pos + 1;
+        st->self_len[tid] = my_self_len + 1;
     }
     if (tid == 0) {
         int nu = 0;

@@ -315,4 +315,30 @@ hipError_t launch_prefill_state(DecState* st, int* ids, const int* prompt, int n
     return hipGetLastError();
 }
 
+// The ragged form (wt_decoder_set_prompt_rows): row b holds lens[b] <= len prompt tokens, `prompt` [B][len] is right-padded (the layout the
+// prefill pass computes over).  The id row is left-padded -- pad x (len - lens[b]), prompt(b), start token -- so that cur_len = len + 1 stays
+// batch-wide and every rule that keys on it is untouched; pos and self_len are the row's own: its start token sits at decoder position
+// lens[b], behind lens[b] valid keys (the filler's keys in cache rows lens[b]..len-1 are overwritten step by step before they are read).
+__global__ void prefill_state_rows_kernel(DecState* st, int* ids, const int* __restrict__ prompt, const int* __restrict__ lens, int len, int B,
+                                          int max_length, int start_token, int pad) {
+    const int t = threadIdx.x;
+    if (t < MAX_ROWS) {
+        const int n = t < B ? min(max(lens[t], 0), len) : len;
+        st->cur_len[t] = len + 1;
+        st->pos[t] = n;
+        st->self_len[t] = n;
+    }
+    if (t == 0) st->done = len + 1 >= max_length ? 1 : 0;
+    for (int i = t; i < B * (len + 1); i += blockDim.x) {
+        const int b = i / (len + 1), j = i - b * (len + 1), lead = len - min(max(lens[b], 0), len);
+        ids[(size_t)b * max_length + j] = j < lead ? pad : j < len ? prompt[(size_t)b * len + (j - lead)] : start_token;
+    }
+}
+hipError_t launch_prefill_state_rows(DecState* st, int* ids, const int* prompt, const int* lens, int len, int B, int max_length, int start_token,
+                                     int pad, hipStream_t s) {
+    if (B < 1 || B > MAX_ROWS || len < 1 || len + 1 > max_length || !lens) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prefill_state_rows_kernel, dim3(1), dim3(256), 0, s, st, ids, prompt, lens, len, B, max_length, start_token, pad);
+    return hipGetLastError();
+}
+
 }  // namespace wt

@@ -180,6 +180,10 @@ hipError_t launch_prefill_embed(const int* prompt, int n_rows, int len, const fl
 // behind launch_dec_init: ids row b = prompt(b), start token; cur_len = len + 1, pos = len, self_len = len for every row
 hipError_t launch_prefill_state(DecState* st, int* ids, const int* prompt, int n_rows, int len, int B, int max_length, int start_token,
                                 hipStream_t s);
+// the ragged form: prompt [B][len] right-padded, lens[B] device; ids row b = pad x (len - lens[b]), prompt(b), start token; cur_len = len + 1 for
+// every row, pos = self_len = lens[b]
+hipError_t launch_prefill_state_rows(DecState* st, int* ids, const int* prompt, const int* lens, int len, int B, int max_length, int start_token,
+                                     int pad, hipStream_t s);
 
 // ---- token-level timestamps: the post-pass over the captured queries and the resident cross-K cache (kernels_token_timestamps.hip) ----
 // Per utterance b and selected head: W[t][s] = softmax_s(q_hist[t] . K[s]); W = (W - mean_t) / std_t (population std over the N tokens);

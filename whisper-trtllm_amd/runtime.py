@@ -240,8 +240,34 @@ def prompt_rows(prompt_ids, batch: int, max_target_positions: int):
     return [r[:1] + r[1:][-keep:] for r in rows]
 
 
+def ragged_prompt_rows(prompts, batch: int, max_target_positions: int):
+    """Per-utterance decoder prompts as the engine takes them (wt_decoder_set_prompt_rows): `prompts` holds one sequence per utterance, each
+    empty (no prompt for that row) or starting with <|startofprev|>; the text part of each is cut to its last max_target_positions // 2 - 1
+    tokens.  Returns `batch` lists of unequal lengths."""
+    if hasattr(prompts, "tolist"):
+        prompts = prompts.tolist()
+    rows = [r.tolist() if hasattr(r, "tolist") else list(r) for r in prompts]
+    if len(rows) != batch:
+        raise ValueError(f"prompts has {len(rows)} rows for a batch of {batch} (one sequence per utterance, empty for none)")
+    keep = max_target_positions // 2 - 1
+    return [[int(t) for t in r[:1] + r[1:][-keep:]] for r in rows]
+
+
+def strip_prompts(ids, prompt_len: int, eos_token_id=None):
+    """The rows of a decode behind decoder prompts (`prompt_ids`, or `prompts` whose rows are left-padded to the longest) without the pad
+    and the prompt: per row the list of ids from the start token on, cut behind the row's first EOS when `eos_token_id` is given."""
+    out = []
+    for row in (ids.tolist() if hasattr(ids, "tolist") else ids):
+        row = [int(t) for t in row[prompt_len:]]
+        if eos_token_id is not None and eos_token_id in row[1:]:
+            row = row[:row.index(eos_token_id, 1) + 1]
+        out.append(row)
+    return out
+
+
 def _check_prompt_args(rows, vocab_size, max_length, num_beams, return_token_timestamps, half_engine):
-    """What the engine refuses (wt_decoder_set_prompt / wt_decoder_begin: WT_E_INVALID, WT_E_UNSUPPORTED), refused before anything is enqueued."""
+    """What the engine refuses (wt_decoder_set_prompt / wt_decoder_set_prompt_rows / wt_decoder_begin: WT_E_INVALID, WT_E_UNSUPPORTED), refused
+    before anything is enqueued.  `rows` may be of unequal lengths (`prompts`): the longest counts."""
     if half_engine:
         raise ValueError("prompt_ids needs an fp32 decoder engine (the prefill is fp32)")
     if num_beams > 1:
@@ -251,8 +277,9 @@ def _check_prompt_args(rows, vocab_size, max_length, num_beams, return_token_tim
     bad = [t for r in rows for t in r if not 0 <= t < vocab_size]
     if bad:
         raise ValueError(f"prompt_ids holds ids outside the vocabulary [0, {vocab_size}): {bad[:4]}")
-    if len(rows[0]) + 2 > max_length:
-        raise ValueError(f"a prompt of {len(rows[0])} tokens, the start token and one generated token exceed max_length {max_length}")
+    longest = max(len(r) for r in rows)
+    if longest + 2 > max_length:
+        raise ValueError(f"a prompt of {longest} tokens, the start token and one generated token exceed max_length {max_length}")
 
 
 class DecodeScores:
@@ -428,7 +455,18 @@ class WhisperDecoderEngine:
                    "wt_decoder_set_logprobs")
         self._lp_ns = no_speech_token_id if on else None
 
-    def _set_prompt(self, rows=None):
+    def _set_prompt(self, rows=None, ragged: bool = False):
+        """`ragged`: rows of unequal lengths (wt_decoder_set_prompt_rows; the two calls replace each other)."""
+        if rows and ragged:
+            width = max(len(r) for r in rows)
+            arr, _n = _i32_array([x for r in rows for x in r + [0] * (width - len(r))])
+            lens, _m = _i32_array([len(r) for r in rows])
+            self._prompt_keep = (arr, lens)
+            _lib.check(self.session._lib.wt_decoder_set_prompt_rows(self.session.handle, ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32)), len(rows),
+                                                                     width, ctypes.cast(lens, ctypes.POINTER(ctypes.c_int32))),
+                       "wt_decoder_set_prompt_rows")
+            self._prompt_len = width
+            return
         t = None
         if rows:
             arr, _n = _i32_array([x for r in rows for x in r])
@@ -508,8 +546,9 @@ class WhisperDecoderEngine:
     def begin(self, encoder_hidden, max_length=None, force_eos_step=None, logits_trace=None, force_eos_steps=None,
               return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
               return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7,
-              return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0, seed: int = 0, seeds=None, prompt_ids=None):
-        """Start a decode (wt_decoder_begin).  `prompt_ids`: a decoder prompt in front of the start token (see `generate`).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
+              return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0, seed: int = 0, seeds=None, prompt_ids=None,
+              prompts=None):
+        """Start a decode (wt_decoder_begin).  `prompt_ids` / `prompts`: a decoder prompt in front of the start token, shared or of one length / per utterance (see `generate`).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
         with `seeds[b]`, or `seed + b` without a list; not with beams.  `return_logprobs` / `no_speech_token_id`: see `generate` (read with `read_logprobs`).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
         the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
         `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
@@ -532,15 +571,22 @@ class WhisperDecoderEngine:
         if force_eos_steps is not None and len(force_eos_steps) != self._B:
             raise ValueError(f"force_eos_steps needs one entry per utterance ({self._B}), got {len(force_eos_steps)}")
         prompt = None
+        if prompt_ids is not None and prompts is not None:
+            raise ValueError("prompt_ids and prompts cannot be combined (one shared / equal-length prompt, or one per utterance)")
         if prompt_ids is not None:
             prompt = prompt_rows(prompt_ids, self._B, i.max_target_positions)
+        elif prompts is not None:
+            prompt = ragged_prompt_rows(prompts, self._B, i.max_target_positions)
+            if not any(prompt):
+                prompt = None                     # all rows empty: no prompt
+        if prompt:
             _check_prompt_args(prompt, i.vocab_size, self.config["max_length"] if max_length is None else max_length, num_beams,
                                return_token_timestamps, i.precision != 0)
-        plen = len(prompt[0]) if prompt else 0
+        plen = max(len(r) for r in prompt) if prompt else 0
         self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, plen)
         self._trace = logits_trace
         self._set_timestamp_rules(return_timestamps, plen)
-        self._set_prompt(prompt)
+        self._set_prompt(prompt, ragged=prompts is not None)
         self._set_beam_search(num_beams, length_penalty, early_stopping)
         self._set_token_timestamps(tt_heads, median_filter_width)
         self._set_logprobs(return_logprobs, no_speech_token_id)
@@ -610,8 +656,12 @@ class WhisperDecoderEngine:
                  lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, return_scores: bool = False, return_token_timestamps: bool = False, alignment_heads=None,
                  median_filter_width: int = 7, return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0,
-                 seed: int = 0, seeds=None, prompt_ids=None):
+                 seed: int = 0, seeds=None, prompt_ids=None, prompts=None):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
+        `prompts`: per-utterance decoder prompts of unequal lengths (several recordings under condition_on_previous_text): one sequence per
+        utterance, each empty or starting with <|startofprev|>, cut like `prompt_ids`; not together with it.  With Lmax the longest, the
+        returned rows are left-padded with pad_token_id to Lmax in front of the start token (`strip_prompts` removes pad and prompt),
+        max_length counts Lmax and DecodeScores carry prompt_len = Lmax (include/whisper_trtllm_amd.h (9h)).  All rows empty: no prompt.
         `prompt_ids`: a decoder prompt (transformers' generate(prompt_ids=...), openai-whisper's initial_prompt / previous text): a 1-D
         sequence shared by the batch or a 2-D [B, n] one with per-row contents of equal length, first entry <|startofprev|>, the text part
         cut to its last max_target_positions // 2 - 1 tokens.  The prompt runs through the decoder in one pass on the device (the prefill,
@@ -638,13 +688,26 @@ class WhisperDecoderEngine:
         row_seeds = _check_sampling_args(temperature, seed, seeds, encoder_hidden, num_beams)
         samp = lambda i, j: {"temperature": temperature, "seeds": row_seeds[i:j]} if row_seeds else {}
         prompt = None
+        if prompt_ids is not None and prompts is not None:
+            raise ValueError("prompt_ids and prompts cannot be combined (one shared / equal-length prompt, or one per utterance)")
+        if prompts is not None:
+            info = self.session.info
+            ragged = ragged_prompt_rows(prompts, encoder_hidden.shape[0], info.max_target_positions)
+            if not any(ragged):
+                prompts = None                    # all rows empty: no prompt
+            else:
+                ml = self.config["max_length"] if max_length is None else max_length
+                _check_prompt_args(ragged, info.vocab_size, ml, num_beams, return_token_timestamps, info.precision != 0)
+                if encoder_hidden.shape[0] > self.max_batch:
+                    return self._generate_ragged_sliced(encoder_hidden, ragged, ml, force_eos_step, logits_trace, chunk, force_eos_steps, lookahead,
+                                                        return_timestamps, return_logprobs, no_speech_token_id, temperature, row_seeds)
         if prompt_ids is not None:   # (begin() checks again on the single-batch path; here the rows are also needed to slice a >16-row batch)
             info = self.session.info
             prompt = prompt_rows(prompt_ids, encoder_hidden.shape[0], info.max_target_positions)
             _check_prompt_args(prompt, info.vocab_size, self.config["max_length"] if max_length is None else max_length, num_beams,
                                return_token_timestamps, info.precision != 0)
         # the prompt rows of utterances i..j (engine batches of a larger batch slice them with the encoder rows)
-        pk = lambda i, j: {"prompt_ids": prompt if len(prompt) == 1 else prompt[i:j]} if prompt else {}
+        pk = lambda i, j: {"prompt_ids": prompt if len(prompt) == 1 else prompt[i:j]} if prompt else ({"prompts": prompts} if prompts is not None else {})
         tt = None
         if return_token_timestamps:
             _check_token_timestamp_args(self.config, self.session.info, True, alignment_heads, median_filter_width, num_beams)
@@ -707,6 +770,34 @@ class WhisperDecoderEngine:
             return (ids, self.read_token_timestamps(cur), scores) if tt else (ids, scores)
         return (self.read_ids(cur), self.read_token_timestamps(cur)) if tt else self.read_ids(cur)
 
+    def _generate_ragged_sliced(self, encoder_hidden, rows, max_length, force_eos_step, logits_trace, chunk, force_eos_steps, lookahead,
+                                return_timestamps, return_logprobs, no_speech_token_id, temperature, row_seeds):
+        """`generate(prompts=...)` over more than 16 utterances: consecutive engine batches, each left-padded to its own longest prompt and
+        with max_length lowered by what that is shorter than the whole batch's, so that every row keeps its budget of generated tokens;
+        the parts are then shifted to the whole batch's longest prompt."""
+        import torch
+        if logits_trace is not None:
+            raise ValueError(f"logits_trace supports at most {self.max_batch} utterances per call")
+        L, pad, step = max(len(r) for r in rows), self.config["pad_token_id"], self.max_batch
+        parts = []
+        for i in range(0, encoder_hidden.shape[0], step):
+            sub = rows[i:i + step]
+            shift = L - max(len(r) for r in sub)
+            out = self.generate(encoder_hidden[i:i + step], max_length - shift, force_eos_step, None, chunk,
+                                None if force_eos_steps is None else force_eos_steps[i:i + step], lookahead, return_timestamps,
+                                return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id,
+                                **({"temperature": temperature, "seeds": row_seeds[i:i + step]} if row_seeds else {}), prompts=sub)
+            parts.append((shift, out))
+        left = lambda x, shift, value: torch.nn.functional.pad(x, (shift, 0), value=value)
+        cat = lambda ps, value: torch.cat([torch.nn.functional.pad(p, (0, max(q.shape[1] for q in ps) - p.shape[1]), value=value) for p in ps], dim=0)
+        if not return_logprobs:
+            return cat([left(o, sh, pad) for sh, o in parts], pad)
+        ids = cat([left(o[0], sh, pad) for sh, o in parts], pad)
+        sc = [o[1] for _sh, o in parts]
+        scores = DecodeScores(ids, cat([left(o[1].token_logprobs, sh, 0.0) for sh, o in parts], 0.0), torch.cat([x.sum_logprob for x in sc]),
+                              torch.cat([x.no_speech_prob for x in sc]) if no_speech_token_id is not None else None, self.config["eos_token_id"], L)
+        return ids, scores
+
     def generate_with_fallback(self, encoder_hidden, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0), compression_ratio_threshold=2.4,
                                logprob_threshold=-1.0, no_speech_threshold=0.6, no_speech_token_id=None, text_of=None, seed: int = 0,
                                seeds=None, **generate_kwargs):
@@ -718,7 +809,10 @@ class WhisperDecoderEngine:
         temperature (or with `seeds[i]`, for a caller whose rows are not consecutive utterances), whichever other rows are decoded beside
         it.  `text_of(ids) -> str` gives the text whose compression ratio is taken
         (default: the config's token decoder, or the ids in decimal).  `prompt_ids` (see `generate`) goes to every try; the EOS is searched
-        behind the prompt and the compression ratio is taken of the text without it.  Returns (ids int32 [B, len] padded with pad_token_id, DecodeScores,
+        behind the prompt and the compression ratio is taken of the text without it.  `prompts` (per-utterance, see `generate`): a try
+        decodes its rows left-padded to ITS longest prompt, with max_length lowered by what that is shorter than the whole batch's -- every
+        row keeps its budget of generated tokens and, drawing at its own positions, its result whichever rows are tried beside it; the
+        returned rows are all left-padded to the whole batch's longest.  Returns (ids int32 [B, len] padded with pad_token_id, DecodeScores,
         temperature_used float32 [B])."""
         import torch
         from .text import compression_ratio
@@ -735,16 +829,37 @@ class WhisperDecoderEngine:
         if len(row_seed) < B:
             raise ValueError(f"seeds needs one entry per utterance ({B}), got {len(row_seed)}")
         prompt = generate_kwargs.pop("prompt_ids", None)
+        ragged = generate_kwargs.pop("prompts", None)
+        if prompt is not None and ragged is not None:
+            raise ValueError("prompt_ids and prompts cannot be combined (one shared / equal-length prompt, or one per utterance)")
         if prompt is not None:
             prompt = prompt_rows(prompt, B, self.session.info.max_target_positions)
         plen = len(prompt[0]) if prompt else 0
+        if ragged is not None:
+            ragged = ragged_prompt_rows(ragged, B, self.session.info.max_target_positions)
+            plen = max(len(r) for r in ragged)
+            if plen == 0:
+                ragged = None
+            else:
+                ml = generate_kwargs.pop("max_length", None)
+                ml = self.config["max_length"] if ml is None else ml
         todo = list(range(B))
         rows = [None] * B                      # per original row: (ids, token_logprobs, sum_logprob, no_speech_prob, temperature)
         for t in temperatures:
             hidden = encoder_hidden if len(todo) == B else encoder_hidden[torch.as_tensor(todo, device=encoder_hidden.device)]
-            ids, sc = self.generate(hidden, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
-                                    seeds=[row_seed[i] for i in todo], **generate_kwargs,
-                                    **({"prompt_ids": prompt if len(prompt) == 1 else [prompt[i] for i in todo]} if prompt else {}))
+            shift = 0
+            if ragged:   # this try's rows at their own longest prompt, then shifted to the whole batch's
+                sub = [ragged[i] for i in todo]
+                shift = plen - max(len(r) for r in sub)
+                ids, sc = self.generate(hidden, max_length=ml - shift, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
+                                        seeds=[row_seed[i] for i in todo], **generate_kwargs, prompts=sub)
+                if shift:
+                    ids = torch.nn.functional.pad(ids, (shift, 0), value=pad)
+                    sc.token_logprobs = torch.nn.functional.pad(sc.token_logprobs, (shift, 0), value=0.0)
+            else:
+                ids, sc = self.generate(hidden, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
+                                        seeds=[row_seed[i] for i in todo], **generate_kwargs,
+                                        **({"prompt_ids": prompt if len(prompt) == 1 else [prompt[i] for i in todo]} if prompt else {}))
             avg = sc.avg_logprob.cpu().tolist()
             nsp = sc.no_speech_prob.cpu().tolist() if sc.no_speech_prob is not None else [None] * len(todo)
             host_ids = ids.cpu().tolist()
@@ -958,6 +1073,13 @@ def transcribe_continuous(enc: "WhisperEncoderEngine", dec: "WhisperDecoderEngin
         stats["steps"] = int(st.n_steps)
         stats["slot_utilisation"] = stats["row_steps"] / float(max(1, st.n_steps) * slots)
     return results
+
+
+def transcribe_long(enc: "WhisperEncoderEngine", dec: "WhisperDecoderEngine", frontend, audios, **options):
+    """Long-form transcription (recordings longer than one window): openai-whisper's seek loop, batched over the recordings of `audios`
+    (1-D float32 GPU tensors) -- see longform.transcribe_long for the options and longform.transcribe for the result."""
+    from . import longform
+    return longform.transcribe_long(enc, dec, frontend, audios, **options)
 
 
 class WhisperPipeline:
