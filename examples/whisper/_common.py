@@ -27,8 +27,14 @@ def load_checkpoint(spec: str):
     cfg = json.load(open(os.path.join(spec, "config.json")))
     gen_path = os.path.join(spec, "generation_config.json")
     if os.path.exists(gen_path):
-        for k, v in json.load(open(gen_path)).items():
+        gen = json.load(open(gen_path))
+        for k, v in gen.items():
             cfg.setdefault(k, v)
+        # multilingual checkpoints: the language / task names of generate(language=..., task=...), and the forced list whose position 1
+        # is the language slot when config.json itself carries none
+        for k in ("lang_to_id", "task_to_id", "forced_decoder_ids"):
+            if cfg.get(k) is None and gen.get(k) is not None:
+                cfg[k] = gen[k]
     cfg.setdefault("forced_bos_token_id", None)
     st_path, bin_path = os.path.join(spec, "model.safetensors"), os.path.join(spec, "pytorch_model.bin")
     if os.path.exists(st_path):

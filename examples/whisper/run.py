@@ -79,6 +79,14 @@ def parse_arguments():
                         "(runtime.transcribe_long); prints [start --> end] text per file; single rank, fp32 decoder engine, no beams")
     parser.add_argument("--no_condition_on_previous_text", action="store_true", help="--long_form: do not prompt a window with the text before it")
     parser.add_argument("--max_rows", type=int, default=8, help="--long_form: recordings decoded side by side (<= 16)")
+    parser.add_argument("--language", type=str, default=None, help="fast path, multilingual checkpoints: auto (detect every utterance's "
+                        "language in the first step of its decode), a code (en), a token (<|en|>) or a token id; prints the language per "
+                        "utterance; needs a batch plan, no beams, no --return_token_timestamps; with --long_form a recording keeps the "
+                        "language of its first window")
+    parser.add_argument("--task", type=str, default=None, help="transcribe | translate (the checkpoint's task_to_id) or a token id: "
+                        "replaces the task token of the forced list")
+    parser.add_argument("--detect_language", action="store_true", help="fast path: only detect and print every utterance's language "
+                        "(one decoder step per batch)")
     parser.add_argument("--length_penalty", type=float, default=1.0)
     parser.add_argument("--early_stopping", action="store_true")
     args = parser.parse_args()
@@ -110,6 +118,16 @@ def parse_arguments():
                      "--return_token_timestamps, --prompt_ids, --temperature (it walks the fallback's list) or --batching continuous")
     if args.long_form and not 1 <= args.max_rows <= 16:
         parser.error("--max_rows must be in [1, 16]")
+    if args.detect_language and args.language is None:
+        args.language = "auto"
+    for key in ("language", "task"):     # ids may be given as numbers
+        v = getattr(args, key)
+        if v is not None and v.lstrip("-").isdigit():
+            setattr(args, key, int(v))
+    if (args.language is not None or args.task is not None) and (args.session or args.compare or args.batching == "continuous"):
+        parser.error("--language / --task / --detect_language need the fast path with a batch plan (--batching sorted | dataset): no --session / --compare")
+    if args.language is not None and (args.num_beams > 1 or args.return_token_timestamps):
+        parser.error("--language takes no beams and no --return_token_timestamps")
     if args.alignment_heads is not None:
         try:
             args.alignment_heads = [tuple(int(x) for x in pair.split(",")) for pair in args.alignment_heads]
@@ -211,6 +229,8 @@ if __name__ == "__main__":
     if args.max_length:
         config["max_length"] = args.max_length
     name = config.get("name", "whisper-tiny.en")
+    lang_name = {v: k for k, v in (config.get("lang_to_id") or {}).items()}
+    show_lang = lambda tok, p: f"language {lang_name.get(tok, tok)}" + ("" if p is None else f"  probability {p:.4f}")
     if args.long_form:
         if world > 1:
             raise SystemExit("--long_form runs on one rank")
@@ -232,14 +252,19 @@ if __name__ == "__main__":
             t0 = time.time()
             files = tensorrt_llm.runtime.transcribe_long(enc, dec, frontend, audios, condition_on_previous_text=not args.no_condition_on_previous_text,
                                                          no_speech_token_id=args.no_speech_token_id, max_rows=args.max_rows, seed=args.seed,
+                                                         **({"language": args.language} if args.language is not None else {}),
+                                                         **({"task": args.task} if args.task is not None else {}),
                                                          **({"text_of": lambda ids: tok.decode(ids, skip_special_tokens=True)} if tok else {}))
             torch.cuda.synchronize()
             elapsed = time.time() - t0
+        file_langs = [None] * len(audios)
+        if args.language is not None:        # (segments per file, dict(language, language_prob) per file)
+            files, file_langs = files
         seconds = sum(a.numel() for a in audios) / tensorrt_llm.audio.SAMPLING_RATE
         print(f"long form   : {elapsed:.3f} s for {seconds:.1f} s of audio in {len(audios)} file(s)  ({seconds / elapsed:.1f} audio-s/s)")
         tb = tensorrt_llm.runtime.timestamp_rules(config)[1]
-        for fname, segments in zip(names, files):
-            print(f"{fname}:")
+        for fname, segments, lang in zip(names, files, file_langs):
+            print(f"{fname}:" + (f"  {show_lang(lang['language'], lang['language_prob'])}" if lang else ""))
             for seg in segments:
                 if tok:
                     text = tok.decode_with_timestamps(seg["ids"])
@@ -276,12 +301,21 @@ if __name__ == "__main__":
         else:
             begin, end = tensorrt_llm.sharding.utterance_shard(len(mels), world, rank)   # this rank's contiguous shard
             groups = [list(range(b0, b1)) for b0, b1 in tensorrt_llm.sharding.batches(begin, end, per_batch)]
+        if args.detect_language:
+            if rank == 0:
+                dec = pipe.engines[0][1]
+                enc = pipe.engines[0][0]
+                for g in groups:
+                    toks, probs = dec.detect_language(enc(torch.cat([mels[i] for i in g])))
+                    for i, t, p in zip(g, toks.cpu().tolist(), probs.max(1).values.cpu().tolist()):
+                        print(f"utterance {i}: {show_lang(t, p)}")
+            raise SystemExit(0)
         for _ in range(2):  # the first pass is the warm-up, as in run.py:260
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.time()
-            indexed, score_rows = [], []
+            indexed, score_rows, lang_rows = [], [], []
             if groups is None:
                 rows = pipe.transcribe_continuous(torch.cat(mels[begin:end]), slots=8, chunk=8) if end > begin else []
                 indexed = list(zip(range(begin, end), [r.tolist() for r in rows]))
@@ -303,8 +337,14 @@ if __name__ == "__main__":
                     kw = [dict(k, prompt_ids=args.prompt_ids) for k in (kw or [{}] * len(groups))]
                 if args.num_beams > 1:
                     kw = [{"num_beams": args.num_beams, "length_penalty": args.length_penalty, "early_stopping": args.early_stopping}] * len(groups)
+                lt = dict(**({"language": args.language} if args.language is not None else {}), **({"task": args.task} if args.task is not None else {}))
+                if lt:
+                    kw = [dict(k, **lt) for k in (kw or [{}] * len(groups))]
                 for g, ids in zip(groups, pipe.transcribe([torch.cat([mels[i] for i in g]) for g in groups], kw)):
                     used = [args.temperature] * len(g)
+                    if args.language is not None:        # the result's last element: DecodeLanguages of the batch
+                        langs, ids = ids[-1], (ids[:-1] if len(ids) > 2 else ids[0])
+                        lang_rows += list(zip(g, zip(langs.ids.cpu().tolist(), langs.prob_of_ids().cpu().tolist())))
                     if args.temperature_fallback:        # (ids, DecodeScores, temperature used per row)
                         used = ids[2].cpu().tolist()
                         ids = ids[:2]
@@ -326,6 +366,8 @@ if __name__ == "__main__":
             results["fast"] = (elapsed, ids)
             if args.return_logprobs:
                 results["scores"] = [row for _, row in sorted(tensorrt_llm.sharding.gather_objects(score_rows, dist))]
+            if args.language is not None:
+                results["languages"] = [row for _, row in sorted(tensorrt_llm.sharding.gather_objects(lang_rows, dist))]
         if rank == 0:
             print(f"fast path   : {results['fast'][0]:.3f} s for {len(mels)} x 30 s on {world} rank(s)  ({30 * len(mels) / results['fast'][0]:.1f} audio-s/s)")
             if args.dump_ids:
@@ -348,6 +390,10 @@ if __name__ == "__main__":
         print(f"Compare Result: same [{len(a) - len(diff)}], diff [{len(diff)}]")
     token_times = results.pop("token_timestamps", None)
     scores = results.pop("scores", None)
+    languages = results.pop("languages", None)
+    if rank == 0 and languages is not None:
+        for i, (t, p) in enumerate(languages):
+            print(f"utterance {i}: {show_lang(t, p if args.language == 'auto' else None)}")
     if rank == 0:
         for key in results:
             print(key, "ids[0][:16] =", results[key][1][0][:16])

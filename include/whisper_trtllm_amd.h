@@ -331,6 +331,26 @@ int wt_decoder_set_prompt(wt_engine* dec, const wt_prompt_params* p);   /* NULL 
  * bitwise the one wt_decoder_set_prompt gives. */
 int wt_decoder_set_prompt_rows(wt_engine* dec, const int32_t* ids, int n_rows, int ld, const int32_t* lens);
 
+/* (9i) language detection and per-row language tokens (openai-whisper's detect_language; multilingual checkpoints whose forced list is
+ * [[1, <|xx|>], [2, task], ...]).  lang_ids: the n_lang language token ids (1..128, any order, distinct, inside the vocabulary, none the
+ * EOS id).  With the mode on, the token appended at the language position -- the sequence position behind decoder_start_token_id, prompt
+ * length + 1, the same for every row also behind per-row prompts (9h) -- is the ROW'S OWN instead of forced_decoder_ids' batch-wide one:
+ * row_tok[b] when that is one of lang_ids, and where it is negative (or row_tok == NULL: every row) the language the model detects.
+ * Detection is a rule of the first step: its final hidden state is the one detect_language computes from the start token alone, so a
+ * small kernel beside the vocabulary projection takes the logits of lang_ids only (the suppress lists do not apply), their softmax and
+ * the argmax (ties: the lowest id; a NaN row: NaN probabilities and the lowest listed id) -- no extra decoder pass.  The position counts
+ * as forced: log-probability (9e) exactly 0, no draw (9f).  Only the first step of a decode with a row to detect launches the kernel;
+ * every other step, and every step with the mode off, is what it was.
+ * wt_decoder_read_languages copies out, stream-ordered, behind the first step: tok DEVICE i32 [batch] (the rows' language tokens) and prob
+ * DEVICE f32 [batch][n_lang] (softmax over lang_ids, in their order; all 0 when no row was left to detect); either may be NULL.
+ * lang_ids / row_tok: host pointers, copied by the call; row_tok holds n_rows >= the next decode's batch entries.  n_lang <= 0 or
+ * lang_ids == NULL: off.  The setting applies from the next wt_decoder_begin on this handle, which returns WT_E_INVALID for ids outside
+ * the rules above, a row entry that is not listed, too few rows, or a language position at or behind the timestamp rules' begin_index - 1,
+ * and refuses (WT_E_UNSUPPORTED) the mode together with beam search (9c) and token-level timestamps (9d); wt_decoder_stream_begin
+ * refuses it.  It combines with the timestamp mode (9b), log-probabilities (9e), sampling (9f) and prompts (9g, 9h); fp32 and fp16 engines. */
+int wt_decoder_set_languages(wt_engine* dec, const int32_t* lang_ids, int n_lang, const int32_t* row_tok, int n_rows);
+int wt_decoder_read_languages(wt_engine* dec, int32_t* tok, float* prob, void* stream);
+
 /* ---- (10) continuous decoding: every utterance stops at its own EOS and its decode slot is refilled at once.
  * The reference gets per-utterance stopping from transcribing one clip at a time (examples/whisper/run.py:219-226; dataset loop
  * cal_wer.py:249-287); a batch started by wt_decoder_begin runs to its longest row.  Here `slots` rows (1..16) stay busy: utterances

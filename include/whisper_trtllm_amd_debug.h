@@ -302,6 +302,15 @@ int wt_dbg_prefill_query_finish(const float* u, const float* h1, const float* r,
 /* the resident self-K (which = 0) or self-V (1) rows of one (layer, head) of the decode in flight: HOST f32 [rows][max_target_positions][64],
  * rows the decode has not written hold whatever the cache held.  fp32 decoder engines only.  Synchronises. */
 int wt_dbg_self_kv_head(wt_engine* dec, int layer, int head, int which, float* out_host, void* stream);
+/* lang_select_kernel alone, launched as the first step of a language-detecting decode launches it (wt_decoder_set_languages): per row b of
+ * x (device f32 [B][d], the residual stream in front of the final LayerNorm; ln_w / ln_b device f32 [d], both NULL: x is used as it is)
+ * z[l] = dot(LayerNorm(x_b), emb[lang_ids[l]]) over emb device [V][d] (f32, or IEEE half with emb_half), lang_prob device f32
+ * [B][n_lang] = softmax(z), and lang_tok device i32 [B]: an entry < 0 becomes the id of the largest z (torch.argmax over the masked
+ * vocabulary: NaN first, equals to the lowest id), an entry >= 0 stays.  lang_ids HOST i32 [n_lang], 1 <= n_lang <= 128, each inside
+ * [0, V); d a multiple of 4, <= 1280; B <= 16.  scratch: device, wt_dbg_lang_select_scratch_bytes(). */
+size_t wt_dbg_lang_select_scratch_bytes(void);
+int wt_dbg_lang_select(const float* x, const float* ln_w, const float* ln_b, const void* emb, int emb_half, const int32_t* lang_ids, int n_lang,
+                       int V, int B, int d, int32_t* lang_tok, float* lang_prob, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -18,7 +18,7 @@ EXPORTS = [
     "wt_engine_open", "wt_engine_clone", "wt_engine_close", "wt_engine_get_info", "wt_engine_gemm_mode", "wt_engine_infer_shapes", "wt_engine_run",
     "wt_encoder_forward", "wt_decoder_begin", "wt_decoder_steps", "wt_decoder_poll", "wt_decoder_run", "wt_decoder_read_ids",
     "wt_decoder_greedy", "wt_decoder_set_timestamp_rules", "wt_decoder_set_beam_search", "wt_decoder_read_beam_scores",
-    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_set_sampling", "wt_decoder_set_prompt", "wt_decoder_set_prompt_rows", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
+    "wt_decoder_set_token_timestamps", "wt_decoder_read_token_timestamps", "wt_decoder_set_logprobs", "wt_decoder_read_logprobs", "wt_decoder_set_sampling", "wt_decoder_set_prompt", "wt_decoder_set_prompt_rows", "wt_decoder_set_languages", "wt_decoder_read_languages", "wt_decoder_stream_begin", "wt_decoder_stream_submit", "wt_decoder_stream_run", "wt_decoder_stream_collect",
     "wt_engine_set_profiling", "wt_engine_get_timer", "wt_decoder_time_cross_attention", "wt_decoder_time_kernel",
     "wt_logmel_create", "wt_logmel_destroy", "wt_logmel_forward", "wt_logmel_forward_windows", "wt_last_error", "wt_abi_version",
 ]
@@ -40,7 +40,8 @@ DEBUG_EXPORTS = ["wt_dbg_gemm", "wt_dbg_gemm_x3", "wt_dbg_gemm_stamps", "wt_dbg_
                  "wt_dbg_decode_attention_state_scratch_bytes", "wt_dbg_decode_attention_state",
                  "wt_dbg_self_attention_then_pair_state_scratch_bytes", "wt_dbg_self_attention_then_pair_state",
                  "wt_dbg_skinny_qkv_hoist", "wt_dbg_skinny_pair_hoisted", "wt_dbg_logmel_stages",
-                 "wt_dbg_prefill_attention", "wt_dbg_prefill_query_finish", "wt_dbg_self_kv_head"]
+                 "wt_dbg_prefill_attention", "wt_dbg_prefill_query_finish", "wt_dbg_self_kv_head",
+                 "wt_dbg_lang_select_scratch_bytes", "wt_dbg_lang_select"]
 
 
 class TensorDesc(Structure):
@@ -144,6 +145,8 @@ def load():
     lib.wt_decoder_set_sampling.argtypes = [c_void_p, POINTER(SamplingParams)]
     lib.wt_decoder_set_prompt.argtypes = [c_void_p, POINTER(PromptParams)]
     lib.wt_decoder_set_prompt_rows.argtypes = [c_void_p, POINTER(c_int32), c_int, c_int, POINTER(c_int32)]
+    lib.wt_decoder_set_languages.argtypes = [c_void_p, POINTER(c_int32), c_int, POINTER(c_int32), c_int]
+    lib.wt_decoder_read_languages.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     lib.wt_decoder_stream_begin.argtypes = [c_void_p, c_int, c_int, POINTER(GreedyParams), c_void_p]
     lib.wt_decoder_stream_submit.argtypes = [c_void_p, c_void_p, c_int, POINTER(c_int32), POINTER(c_int32), c_void_p]
     lib.wt_decoder_stream_run.argtypes = [c_void_p, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_void_p]
@@ -241,6 +244,9 @@ def load():
     lib.wt_dbg_prefill_attention.argtypes = [P, P, P, P, I, I, I, I, I, I, I, I, F, P]
     lib.wt_dbg_prefill_query_finish.argtypes = [P, P, P, P, P, I, I, P]
     lib.wt_dbg_self_kv_head.argtypes = [c_void_p, I, I, I, P, P]
+    lib.wt_dbg_lang_select_scratch_bytes.argtypes = []
+    lib.wt_dbg_lang_select_scratch_bytes.restype = c_size_t
+    lib.wt_dbg_lang_select.argtypes = [P, P, P, P, I, POINTER(c_int32), I, I, I, I, P, P, P, P]
     if lib.wt_abi_version() != ABI_VERSION:
         raise EngineLibraryError(f"ABI version mismatch: library {lib.wt_abi_version()}, python {ABI_VERSION}")
     _lib = lib

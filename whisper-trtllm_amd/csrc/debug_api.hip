@@ -913,3 +913,18 @@ extern "C" int wt_dbg_prefill_attention(const float* q, const float* kcache, con
 extern "C" int wt_dbg_prefill_query_finish(const float* u, const float* h1, const float* r, const float* t, float* q, int rows, int d, void* stream) {
     return rc_of(launch_prefill_query_finish(u, h1, r, t, q, rows, d, (hipStream_t)stream));
 }
+
+// ---- lang_select_kernel alone, built by the engine's own helper (wt_common.h: lang_select_params) ----
+extern "C" size_t wt_dbg_lang_select_scratch_bytes(void) { return dbg_align((size_t)LANG_MAX * 4); }
+extern "C" int wt_dbg_lang_select(const float* x, const float* ln_w, const float* ln_b, const void* emb, int emb_half, const int32_t* lang_ids,
+                                  int n_lang, int V, int B, int d, int32_t* lang_tok, float* lang_prob, void* scratch, void* stream) {
+    if (!x || !emb || !lang_ids || !lang_tok || !lang_prob || !scratch || (ln_w == nullptr) != (ln_b == nullptr)) return -22;
+    if (B < 1 || B > MAX_ROWS || n_lang < 1 || n_lang > LANG_MAX || V < 1 || d < 4 || d > LANG_D_MAX || (d & 3)) return -22;
+    for (int i = 0; i < n_lang; ++i)   // the kernel reads embedding row lang_ids[i]: inside the table
+        if (lang_ids[i] < 0 || lang_ids[i] >= V) return -22;
+    hipStream_t s = (hipStream_t)stream;
+    int rc = rc_of(hipMemcpyAsync(scratch, lang_ids, (size_t)n_lang * 4, hipMemcpyHostToDevice, s));
+    if (rc || (rc = rc_of(hipStreamSynchronize(s)))) return rc;   // (pageable source)
+    const LangSelectParams p = lang_select_params(x, ln_w, ln_b, emb, emb_half, (const int*)scratch, n_lang, B, d, lang_tok, lang_prob);
+    return rc_of(launch_lang_select(p, s));
+}

@@ -164,16 +164,21 @@ struct wt_engine {
     int* tt_sel = nullptr;        // device [L][H]: selection index of (layer, head), or -1
     uint8_t* tt_trace = nullptr;
     std::vector<int> tt_h_sel;    // host image of tt_sel
+    // per-row language tokens (wt_decoder_set_languages): one device table, the rows' tokens [MAX_ROWS] in front of the listed ids [LANG_MAX]
+    int *lang_tok = nullptr, *lang_ids = nullptr;
+    float* lang_prob = nullptr;   // [MAX_ROWS][LANG_MAX] (rows of n_lang entries): lang_select_kernel's softmax over the listed ids
+    std::vector<int> h_lang;      // host image of that table for the decode in flight (source of an async copy)
     std::vector<int> h_prompt;    // ragged decoder prompt: the right-padded id matrix + lengths of the decode in flight (source of an async copy)
     char* pf_ws = nullptr;        // decoder prompt: the prefill's workspace (allocated by the first prompt decode, grown when needed)
     size_t pf_bytes = 0;
     hipStream_t own_stream = nullptr;
     // step graphs: [0] every row attends (the only one a decode without early finishers ever replays), [1] finished rows stream no K/V,
-    // [2] / [3] the same two for the continuous mode (per-slot cross-cache rows, stream_finish_kernel)
-    static constexpr int N_GRAPHS = 4;
-    hipGraph_t graph[N_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};
-    hipGraphExec_t graph_exec[N_GRAPHS] = {nullptr, nullptr, nullptr, nullptr};
-    bool graph_ok[N_GRAPHS] = {false, false, false, false};
+    // [2] / [3] the same two for the continuous mode (per-slot cross-cache rows, stream_finish_kernel), [4] / [5] the first step of a
+    // decode that detects languages ([0] / [1] with lang_select_kernel in front of the finish; [6] / [7] unused)
+    static constexpr int N_GRAPHS = 8;
+    hipGraph_t graph[N_GRAPHS] = {};
+    hipGraphExec_t graph_exec[N_GRAPHS] = {};
+    bool graph_ok[N_GRAPHS] = {};
     StepKey graph_key = {};       // the key the graphs were captured under (B == 0: none yet); enqueue_steps drops them when cfg.key differs
     int graph_captures = 0;       // step-graph captures of this handle so far (wt_dbg_step_graph_captures)
     bool use_graph = true;
@@ -706,6 +711,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     const size_t o_banc = take((size_t)2 * MAX_ROWS * cap_len * 4), o_burow = take(MAX_ROWS * 4), o_bhn = take(MAX_ROWS * 4), o_bhd = take(MAX_ROWS * 4);
     const size_t o_bhw = take(MAX_ROWS * 8), o_bhs = take(MAX_ROWS * 8), o_bhl = take(MAX_ROWS * 4), o_bhi = take((size_t)MAX_ROWS * cap_len * 4);
     const size_t o_bout = take((size_t)MAX_ROWS * cap_len * 4), o_bos = take(MAX_ROWS * 4), o_btr = take((size_t)cap_len * MAX_ROWS * 4 * 4);
+    const size_t o_lang = take((size_t)(MAX_ROWS + LANG_MAX) * 4), o_langp = take((size_t)MAX_ROWS * LANG_MAX * 4);
     hipError_t he = hipMalloc((void**)&e->dec_ws, off);
     if (he != hipSuccess) return fail(WT_E_NOMEM, "hipMalloc(%zu) for decoder workspace (batch %d) failed: %s", off, B, hipGetErrorString(he));
     char* b = e->dec_ws;
@@ -715,6 +721,7 @@ static int dec_reserve(wt_engine* e, int B, int max_length, hipStream_t s, int p
     e->logits = (float*)(b + o_lg); e->st = (DecState*)(b + o_st); e->ids = (int*)(b + o_ids); e->unfinished = (int*)(b + o_unf);
     e->forced = (int*)(b + o_forced); e->mask = (uint8_t*)(b + o_mask); e->force_rows = (int*)(b + o_frows); e->ts_part = (TsPart*)(b + o_tsp);
     e->lp_part = (float4*)(b + o_lpp); e->lp_side = (float*)(b + o_lps); e->lp_tok = (float*)(b + o_lpt); e->lp_sum = (float*)(b + o_lpsum); e->lp_nsp = (float*)(b + o_lpn);
+    e->lang_tok = (int*)(b + o_lang); e->lang_ids = e->lang_tok + MAX_ROWS; e->lang_prob = (float*)(b + o_langp);
     e->samp_seeds = (unsigned long long*)(b + o_sseed); e->samp_sc = (float*)(b + o_ssc); e->samp_ts = (float4*)(b + o_sts);
     {
         BeamParams& bp = e->beam_dev;
@@ -766,6 +773,7 @@ struct StepIO {
     // greedy fast path: masked argmax fused into the vocabulary GEMV (logits == nullptr: they never reach HBM unless traced)
     const SelectParams* argmax;            // or nullptr: write plain logits
     int* argmax_parts;                     // out: partial results per batch row (workgroups of the GEMV)
+    bool lang = false;                     // language detection: lang_select_kernel on the final hidden state, beside the vocabulary stage
 };
 
 // The seven dependent launches of decoder layer i (model.py:321-369).  h = residual stream in, h1 = the other buffer of the
@@ -883,6 +891,11 @@ static int enqueue_step(wt_engine* e, const StepIO& io, hipStream_t s) {
         *io.argmax_parts = grid;
     }
     TIMED(e, e->t_skinny, s, launch_skinny(k, s));
+    if (io.lang) {   // the first step of a decode that detects languages: the rows' language tokens, in front of the finish kernel that appends them
+        const LangSelectParams lp = lang_select_params(h, e->dec_ln_w, e->dec_ln_b, e->proj_w, e->w_half, e->lang_ids, e->cfg.key.n_lang, B, d,
+                                                       e->lang_tok, e->lang_prob);
+        LAUNCH(launch_lang_select(lp, s));
+    }
     return WT_OK;
 }
 
@@ -1172,6 +1185,33 @@ extern "C" int wt_decoder_set_prompt_rows(wt_engine* e, const int32_t* ids, int 
     return WT_OK;
 }
 
+extern "C" int wt_decoder_set_languages(wt_engine* e, const int32_t* lang_ids, int n_lang, const int32_t* row_tok, int n_rows) {
+    if (!e || e->kind != WT_KIND_DECODER) return fail(WT_E_INVALID, "wt_decoder_set_languages: not a decoder engine");
+    if (n_lang <= 0 || !lang_ids) {
+        e->req.lang_ids.clear();
+        e->req.lang_rows.clear();
+        return WT_OK;
+    }
+    if (n_lang > LANG_MAX) return fail(WT_E_INVALID, "wt_decoder_set_languages: %d language ids > %d", n_lang, LANG_MAX);
+    if (row_tok && n_rows < 1) return fail(WT_E_INVALID, "wt_decoder_set_languages: a row table of %d entries", n_rows);
+    e->req.lang_ids.assign(lang_ids, lang_ids + n_lang);   // (the ids themselves are checked against the next decode's rules: resolve_decode_config)
+    e->req.lang_rows.clear();
+    if (row_tok) e->req.lang_rows.assign(row_tok, row_tok + n_rows);
+    return WT_OK;
+}
+
+extern "C" int wt_decoder_read_languages(wt_engine* e, int32_t* tok, float* prob, void* stream) {
+    if (!e || e->kind != WT_KIND_DECODER || !e->begun || e->cfg.key.n_lang == 0)
+        return fail(WT_E_STATE, "wt_decoder_read_languages: no decode with per-row language tokens in flight (wt_decoder_set_languages, then wt_decoder_begin)");
+    if (!tok && !prob) return fail(WT_E_INVALID, "wt_decoder_read_languages: null outputs");
+    DeviceGuard guard(e->device);
+    HIPCHK(guard.err);
+    hipStream_t s = (hipStream_t)stream;
+    if (tok) HIPCHK(hipMemcpyAsync(tok, e->lang_tok, (size_t)e->cfg.key.B * 4, hipMemcpyDeviceToDevice, s));
+    if (prob) HIPCHK(hipMemcpyAsync(prob, e->lang_prob, (size_t)e->cfg.key.B * e->cfg.key.n_lang * 4, hipMemcpyDeviceToDevice, s));
+    return WT_OK;
+}
+
 // The prefill (DESIGN.md "Decoder prompts"): positions 0..len-1 of all B rows through the decoder layers in one pass over M = B * len rows
 // (utterance-major), leaving their keys and values in rows 0..len-1 of the resident self caches.  The kernels are the encoder's
 // (launch_layernorm, launch_gemm_f32) and kernels_prefill.hip's; the cross K/V of this decode must be enqueued on `s` before.  The last
@@ -1270,6 +1310,13 @@ extern "C" int wt_decoder_begin(wt_engine* e, const float* enc_hidden, int B, co
         HIPCHK(hipMemsetAsync(e->lp_nsp, 0, (size_t)B * 4, s));
         HIPCHK(hipMemsetAsync(e->lp_side, 0, (size_t)B * 2 * 4, s));
     }
+    if (k.n_lang > 0) {   // the rows' language tokens (-1: lang_select_kernel fills it in the first step) and the listed ids
+        e->h_lang.assign(MAX_ROWS + LANG_MAX, -1);
+        memcpy(e->h_lang.data(), c.lang_rows, (size_t)B * 4);
+        memcpy(e->h_lang.data() + MAX_ROWS, c.lang_ids, (size_t)k.n_lang * 4);
+        HIPCHK(hipMemcpyAsync(e->lang_tok, e->h_lang.data(), e->h_lang.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(e->lang_prob, 0, (size_t)B * k.n_lang * 4, s));   // (rows all chosen by the caller: no kernel runs, the probabilities read 0)
+    }
     LAUNCH(launch_dec_init(e->st, e->ids, e->unfinished, B, k.max_length, k.start_token, e->epoch, s));
     if (k.beam.num_beams > 1) {
         SelectParams sp;
@@ -1330,13 +1377,14 @@ static void fill_select_params(wt_engine* e, SelectParams& sp) {
             sp.samp_K = e->d; sp.samp_parts_cap = SEL_PARTS_CAP;
         }
     }
+    if (k.lang_pos > 0) { sp.lang_pos = k.lang_pos; sp.lang_tok = e->lang_tok; }
     if (e->cfg.stream) {
         sp.stream = 1; sp.host_ids = e->h_ids_dev; sp.host_len = e->h_len_dev; sp.force_eos_step = -1;
     }
 }
 
 // the StepIO of one step of the decode in flight over the resident caches.  variant bit 0: finished / idle rows stream no K/V (`alive`);
-// bit 1: the continuous mode's graph (per-slot cross-cache rows and state)
+// bit 1: the continuous mode's graph (per-slot cross-cache rows and state); bit 2: the first step of a decode that detects languages
 static StepIO step_io(const wt_engine* e, int variant) {
     const StepKey& k = e->cfg.key;
     StepIO io;
@@ -1349,6 +1397,7 @@ static StepIO step_io(const wt_engine* e, int variant) {
     io.nsplit_self = k.nsplit_self; io.nsplit_cross = k.nsplit_cross; io.nt = k.nt_loads;
     io.embed = false;  // dh already holds this step's input: written by wt_decoder_begin (step 0) or by the previous greedy_finish
     io.argmax = nullptr; io.argmax_parts = nullptr;
+    io.lang = (variant & 4) != 0;
     return io;
 }
 
@@ -1378,11 +1427,19 @@ static std::mutex g_capture_mutex;
 // no K/V (wt_decoder_run switches to it once the mailbox reports a finished row; never with a logits trace, which records every
 // row's logits at every step as the reference computes them).  The continuous mode replays variants 2 / 3.
 static int enqueue_steps(wt_engine* e, int n_steps, hipStream_t s, int variant = 0) {
+    if (e->cfg.lang_detect && e->issued == 0 && n_steps > 0 && !(variant & 4)) {   // the first step behind wt_decoder_begin detects the languages:
+        const int rc = enqueue_steps(e, 1, s, variant | 4);                            // its own graph; every later step is what it is without the mode
+        if (rc || n_steps == 1) return rc;
+        n_steps -= 1;
+    }
     StepKey k = e->cfg.key;
     k.workspace_gen = e->ws_gen;   // as it stands NOW: a (re)allocation behind the last begin must not replay graphs into freed memory
+    const int lang_bit = variant & 4;
+    variant &= 3;
     if (k.logits_trace || k.beam.num_beams > 1) variant = 0;   // (beam search: one graph; a finished utterance's rows keep attending)
     if (k.tt.n_sel > 0) variant = 0;   // token-level timestamps: finished rows keep stepping on pad input, their steps are part of the alignment
     if (e->cfg.stream) variant |= 2;
+    variant |= lang_bit;
     if (e->profiling || !e->use_graph) {  // eager: per-kernel event timers need real launches
         for (int i = 0; i < n_steps; ++i) {
             int rc = enqueue_fast_step(e, s, variant);

@@ -206,6 +206,8 @@ int resolve_decode_config(const EngineDims& e, const DecodeFacts& f, const Decod
         if (r.lp.enabled) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: token log-probabilities are a batch-decode feature (wt_decoder_begin)");
         if (r.samp_temp > 0.f) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: temperature sampling is a batch-decode feature (wt_decoder_begin)");
         if (r.prompt_len > 0) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: decoder prompts are a batch-decode feature (wt_decoder_begin)");
+        if (!r.lang_ids.empty())
+            return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: per-row language tokens are a batch-decode feature (wt_decoder_begin)");
         if (p->logits_trace || p->force_eos_step >= 0 || p->force_eos_steps)
             return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_stream_begin: logits_trace / force_eos_step(s) belong to wt_decoder_begin (per-utterance lengths: wt_decoder_stream_submit)");
     } else {
@@ -272,6 +274,38 @@ int resolve_decode_config(const EngineDims& e, const DecodeFacts& f, const Decod
                         tok, idx, k.ts.begin_index - 1);
         if (nb > 1 && tok == p->eos_token_id)
             return fail(err, errlen, WT_E_INVALID, "beam search: forced token %d is the EOS token (no beam could continue)", tok);
+    }
+    k.lang_pos = -1;
+    if (!r.lang_ids.empty()) {   // per-row language tokens (wt_decoder_set_languages): row b's forced token at position prompt + 1 is its own
+        const int n = (int)r.lang_ids.size();
+        if (nb > 1) return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: per-row language tokens and beam search cannot be combined");
+        if (r.tt.n_sel > 0)
+            return fail(err, errlen, WT_E_UNSUPPORTED, "wt_decoder_begin: per-row language tokens and token-level timestamps cannot be combined");
+        if (n > LANG_MAX) return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: %d language ids > %d", n, LANG_MAX);
+        for (int i = 0; i < n; ++i) {
+            const int tok = r.lang_ids[i];
+            if (!tok_ok(tok)) return fail(err, errlen, WT_E_INVALID, "language id %d outside the vocabulary", tok);
+            if (tok == p->eos_token_id) return fail(err, errlen, WT_E_INVALID, "language id %d is the EOS token", tok);
+            for (int j = 0; j < i; ++j)
+                if (r.lang_ids[j] == tok) return fail(err, errlen, WT_E_INVALID, "language id %d listed twice", tok);
+            out->lang_ids[i] = tok;
+        }
+        if (!r.lang_rows.empty() && (int)r.lang_rows.size() < B)
+            return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: wt_decoder_set_languages gave %d row entries for a batch of %d", (int)r.lang_rows.size(), B);
+        for (int b = 0; b < B; ++b) {
+            const int tok = r.lang_rows.empty() ? -1 : r.lang_rows[b];
+            bool listed = tok < 0;
+            for (int i = 0; i < n && !listed; ++i) listed = r.lang_ids[i] == tok;
+            if (!listed) return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: row %d's language token %d is not one of the listed ids", b, tok);
+            out->lang_rows[b] = tok < 0 ? -1 : tok;
+            if (tok < 0) out->lang_detect = 1;
+        }
+        k.lang_pos = out->prompt_len + 1;   // the position behind the start token; batch-wide also for ragged prompts (left-padded rows)
+        k.n_lang = n;
+        if (k.lang_pos >= p->max_length)
+            return fail(err, errlen, WT_E_INVALID, "wt_decoder_begin: the language position %d lies outside max_length %d", k.lang_pos, p->max_length);
+        if (k.ts.enabled && k.lang_pos >= k.ts.begin_index - 1)   // Force and Timestamp must not fight
+            return fail(err, errlen, WT_E_INVALID, "timestamp mode: the language position %d is not in front of begin_index - 1 = %d", k.lang_pos, k.ts.begin_index - 1);
     }
     if (r.tt.n_sel > 0) {   // the query history the cross-attention launches fill: [n_sel][B][max_length - 1][64]
         if (p->max_length - 1 > TT_MAX_TOKENS) return fail(err, errlen, WT_E_UNSUPPORTED, "token timestamps: %d steps > %d", p->max_length - 1, TT_MAX_TOKENS);

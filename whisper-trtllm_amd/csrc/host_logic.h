@@ -21,6 +21,7 @@ constexpr int MAX_BEAMS = 8;
 constexpr int TT_MAX_HEADS = 32;
 constexpr int TT_MAX_WIDTH = 15;
 constexpr int TT_MAX_TOKENS = 1024;   // N of one DTW workgroup (one thread per token row)
+constexpr int LANG_MAX = 128;         // language ids of wt_decoder_set_languages (lang_select_kernel stages one logit per id in LDS)
 
 // ---- serialized engine layout, written by whisper-trtllm_amd/engine_pack.py --------------------------------
 // [BlobHeader][BlobTensor * n_tensors][raw tensor bytes, each 256-byte aligned]
@@ -64,7 +65,7 @@ int infer_shapes(const EngineDims& e, const wt_tensor_desc* in, int n_in, wt_ten
                  char* err, size_t errlen);
 
 // ---- decode configuration -------------------------------------------------------------------------------------
-// What the six wt_decoder_set_* calls asked for; the next wt_decoder_begin / wt_decoder_stream_begin resolves it.  Only the setters write it.
+// What the wt_decoder_set_* calls asked for; the next wt_decoder_begin / wt_decoder_stream_begin resolves it.  Only the setters write it.
 struct DecodeRequest {
     wt_timestamp_params ts = {0, 0, 0, 0, 0};   // enabled == 0: off
     wt_logprob_params lp = {0, -1};             // enabled == 0: off
@@ -81,12 +82,14 @@ struct DecodeRequest {
     std::vector<int> prompt;                    // [prompt_rows][prompt_len]; len 0: off
     int prompt_rows = 0, prompt_len = 0;
     std::vector<int> prompt_lens;               // wt_decoder_set_prompt_rows: tokens of each row of `prompt` ([prompt_rows][prompt_len]); empty: every row holds prompt_len
+    std::vector<int> lang_ids;                  // wt_decoder_set_languages: the language token ids; empty: off
+    std::vector<int> lang_rows;                 // ... and the rows' own: a listed id, or negative = detect; empty: detect every row
 };
 
 // Exactly the values a captured step graph bakes into kernel arguments: the graphs are replayed while the key of the decode in flight
 // equals the key they were captured under, and dropped when it does not (enqueue_steps).  A POD created zero-filled, padding included
 // (resolve_decode_config), so that two keys compare bytewise.  NOT in it, because no captured launch carries them: the contents of the
-// suppress / forced tables and the per-row forced lengths (device tables at fixed addresses), the seeds (a device table), the prompt
+// suppress / forced tables, the per-row forced lengths and the language tables (device tables at fixed addresses), the seeds (a device table), the prompt
 // (prefilled before the first step; the steps read positions from the device state) and the median width / time precision of the
 // token timestamps (arguments of the post-pass only).
 struct StepKey {
@@ -104,13 +107,15 @@ struct StepKey {
     int nt_loads;              // stream weights and K/V with non-temporal loads
     int nsplit_self, nsplit_cross;
     unsigned workspace_gen;    // the engine's count of workspace (re)allocations: the graphs carry device and pinned addresses
+    int lang_pos;              // per-row language tokens: the sequence position whose forced token is the row's own (prompt_len + 1), -1: off ...
+    int n_lang;                // ... and the listed language ids (the first step's lang_select launch), 0: off
     int reserved;              // 0: rounds the struct up to its alignment, so that it has no padding at all
     bool operator==(const StepKey& o) const { return memcmp(this, &o, sizeof *this) == 0; }
     bool operator!=(const StepKey& o) const { return !(*this == o); }
 };
 
 static_assert(sizeof(StepKey) == 8 * sizeof(int) + sizeof(float*) + sizeof(wt_timestamp_params) + sizeof(wt_beam_params) + sizeof(wt_logprob_params) +
-                                     (10 + 2 * TT_MAX_HEADS) * sizeof(int), "StepKey has padding");
+                                     (12 + 2 * TT_MAX_HEADS) * sizeof(int), "StepKey has padding");
 
 // The decode in flight: the step key, and what only the host or the post-pass reads.  A stream decode has every batch-only feature off.
 struct DecodeConfig {
@@ -123,6 +128,9 @@ struct DecodeConfig {
     int prompt_lens[MAX_ROWS];     // ... these are the rows' own, and the id rows are left-padded to prompt_len
     int tt_width;              // token timestamps: median filter width and seconds per encoder frame
     double tt_time_precision;
+    int lang_detect;               // per-row language tokens: some row's entry is negative, so the first step runs lang_select_kernel
+    int lang_ids[LANG_MAX];        // the key.n_lang listed ids ...
+    int lang_rows[MAX_ROWS];       // ... and the rows' entries as the host uploads them (a listed id, or -1 = detect)
 };
 
 // What resolve_decode_config needs to know of the engine beyond its dimensions, and the A/B tuning switches (it reads no environment).
@@ -141,6 +149,7 @@ int pick_splits(int B, int H, int len);   // key splits of the cross-attention l
 // The one place that decides whether the request, the call's parameters and the engine go together, and what the decode then runs with:
 // every compatibility and range check of wt_decoder_begin (`rows` utterances) and wt_decoder_stream_begin (`rows` slots over `pool_rows`
 // cache rows, <= 0: 4 x slots), the token-id checks of the rule tables, B = U * num_beams, "sampling on" -> "log-probability kernels on",
+// the language tables (ids inside the vocabulary, distinct, none the EOS id, row entries negative or listed),
 // and the arithmetic tuning choices (nt_loads, the key splits, beam_group).  Pure.  Returns WT_OK or a WT_E_* code with a message in err;
 // *out is complete only on WT_OK (key.workspace_gen stays 0: the engine fills it where it compares keys).
 int resolve_decode_config(const EngineDims& e, const DecodeFacts& f, const DecodeRequest& r, const wt_greedy_params* p, int rows, int pool_rows,

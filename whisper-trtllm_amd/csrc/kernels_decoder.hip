@@ -1770,7 +1770,8 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
         }
         return;
     }
-    const int forced = p.forced[cur_len];                          // ForceTokensLogitsProcessor
+    // ForceTokensLogitsProcessor; at the language position the row's own token (host-chosen, or lang_select_kernel's earlier in this step)
+    const int forced = p.lang_pos > 0 && cur_len == p.lang_pos ? p.lang_tok[bc] : p.forced[cur_len];
     const int row_eos = p.force_eos_rows ? p.force_eos_rows[bc] : -1;
     int tok;
     LpPick pick;
@@ -1846,6 +1847,92 @@ __global__ __launch_bounds__(256) void greedy_finish_kernel(const SelectParams p
     }
     if (!p.next_x || cur_len + 1 >= p.max_length) return;
     finish_embed(p, s_tok, s_pos, tid);
+}
+
+// ---- language detection (wt_decoder_set_languages): openai-whisper's detect_language as a rule of the first step.  The step whose input is
+// the start token already holds the hidden state detect_language computes, so one workgroup per row takes the logits of the listed
+// language ids alone -- z[l] = dot(LayerNorm(x_b), E[lang_ids[l]]), the suppress lists do not apply --, their softmax and the argmax with
+// torch.argmax's semantics over the masked vocabulary (NaN beats every number, equals go to the LOWEST TOKEN ID).  Every reduction runs in
+// one fixed order inside the row's own workgroup: a row's result depends neither on its slot nor on B.  The embedding rows (<= 128 x d
+// x 4 B) come from L2 once the first workgroup has read them.
+__device__ __forceinline__ bool lang_better(const float az, const int ai, const float bz, const int bi) {
+    const bool an = az != az, bn = bz != bz;
+    if (an != bn) return an;
+    if (!an && az != bz) return az > bz;
+    return ai < bi;
+}
+__global__ __launch_bounds__(256) void lang_select_kernel(const LangSelectParams p) {
+    __shared__ float4 xs[LANG_D_MAX / 4];
+    __shared__ float zs[LANG_MAX];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int d = p.d, d4 = d >> 2;
+    const float4* xrow = reinterpret_cast<const float4*>(p.x + (size_t)b * d);
+    for (int i = tid; i < d4; i += 256) xs[i] = xrow[i];
+    __syncthreads();
+    if (p.ln_w) {   // every wave takes the statistics of the whole row, in the same order: no exchange between waves
+        float sum = 0.f;
+        for (int i = lane; i < d4; i += 64) sum += (xs[i].x + xs[i].y) + (xs[i].z + xs[i].w);
+        const float mean = wave_allreduce_sum_d(sum) / d;
+        float q = 0.f;
+        for (int i = lane; i < d4; i += 64) {
+            const float a = xs[i].x - mean, c = xs[i].y - mean, e = xs[i].z - mean, f = xs[i].w - mean;
+            q += (a * a + c * c) + (e * e + f * f);
+        }
+        const float rstd = rsqrtf(wave_allreduce_sum_d(q) / d + 1e-5f);
+        __syncthreads();   // every wave has read the raw row
+        for (int i = tid; i < d4; i += 256) {
+            const float4 v = xs[i], g = reinterpret_cast<const float4*>(p.ln_w)[i], be = reinterpret_cast<const float4*>(p.ln_b)[i];
+            xs[i] = make_float4((v.x - mean) * rstd * g.x + be.x, (v.y - mean) * rstd * g.y + be.y, (v.z - mean) * rstd * g.z + be.z,
+                                (v.w - mean) * rstd * g.w + be.w);
+        }
+        __syncthreads();
+    }
+    // a wave per language: 16-byte loads of the embedding row (d4 <= 5 x 64 chunks, all requested before the first use)
+    for (int l = wave; l < p.n_lang; l += 4) {
+        const size_t row = (size_t)p.lang_ids[l] * d;
+        float4 ev[LANG_D_MAX / 256];
+#pragma unroll
+        for (int v = 0; v < LANG_D_MAX / 256; ++v) {
+            const int i = lane + 64 * v;
+            ev[v] = i < d4 ? load_emb4(p.emb, row + 4 * (size_t)i, p.emb_half != 0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        float acc = 0.f;
+#pragma unroll
+        for (int v = 0; v < LANG_D_MAX / 256; ++v) {
+            const int i = lane + 64 * v;
+            if (i < d4) acc += dot4(xs[i], ev[v]);
+        }
+        acc = wave_allreduce_sum_d(acc);
+        if (lane == 0) zs[l] = acc;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    const int l0 = lane, l1 = lane + 64;
+    const float z0 = l0 < p.n_lang ? zs[l0] : -INFINITY, z1 = l1 < p.n_lang ? zs[l1] : -INFINITY;
+    float m = fmaxf(z0, z1);   // (fmaxf drops a NaN: the maximum of the numbers; a NaN logit then makes the sum, and every probability, NaN)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    const float e0 = l0 < p.n_lang ? expf(z0 - m) : 0.f, e1 = l1 < p.n_lang ? expf(z1 - m) : 0.f;
+    const float sum = wave_allreduce_sum_d(e0 + e1);
+    if (l0 < p.n_lang) p.lang_prob[(size_t)b * p.n_lang + l0] = e0 / sum;
+    if (l1 < p.n_lang) p.lang_prob[(size_t)b * p.n_lang + l1] = e1 / sum;
+    const int i0 = l0 < p.n_lang ? p.lang_ids[l0] : 0x7fffffff, i1 = l1 < p.n_lang ? p.lang_ids[l1] : 0x7fffffff;
+    float bz = z0;
+    int bi = i0;
+    if (lang_better(z1, i1, bz, bi)) { bz = z1; bi = i1; }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {   // a strict total order over distinct ids: the winner does not depend on the order of the exchange
+        const float oz = __shfl_xor(bz, o);
+        const int oi = __shfl_xor(bi, o);
+        if (lang_better(oz, oi, bz, bi)) { bz = oz; bi = oi; }
+    }
+    if (lane == 0 && p.lang_tok[b] < 0) p.lang_tok[b] = bi;
+}
+hipError_t launch_lang_select(const LangSelectParams& p, hipStream_t s) {
+    if (!p.x || !p.emb || !p.lang_ids || !p.lang_tok || !p.lang_prob || (p.ln_w == nullptr) != (p.ln_b == nullptr)) return hipErrorInvalidValue;
+    if (p.B < 1 || p.B > MAX_ROWS || p.n_lang < 1 || p.n_lang > LANG_MAX || p.d < 4 || p.d > LANG_D_MAX || (p.d & 3)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lang_select_kernel, dim3(p.B), dim3(256), 0, s, p);
+    return hipGetLastError();
 }
 
 // ---- continuous mode (wt_decoder_stream_*): every slot at its own position; a row that stops is replaced AT ONCE, by this kernel, with

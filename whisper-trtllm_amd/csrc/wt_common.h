@@ -413,7 +413,25 @@ struct SelectParams {
     float* samp_sc;
     float4* samp_ts;
     float* samp_key;
+    // per-row language tokens (lang_pos > 0; wt_decoder_set_languages): at cur_len == lang_pos the forced token of row b is lang_tok[b]
+    // instead of forced[cur_len] (written by the host, or by lang_select_kernel earlier in that step)
+    int lang_pos;
+    const int* lang_tok;             // [B]
 };
+// Language detection, a rule of the first step (DESIGN.md "Language detection"): per row the logits of the listed language ids alone, from
+// the residual stream entering the final LayerNorm, their softmax and the winning id.
+struct LangSelectParams {
+    const float* x;                  // [B][d] the step's final hidden state, in front of the final LayerNorm
+    const float *ln_w, *ln_b;        // the final LayerNorm (nullptr: x is used as it is)
+    const float* emb;                // the tied embedding / projection matrix [V][d]: fp32, or IEEE half with emb_half
+    int emb_half;
+    const int* lang_ids;             // [n_lang] token ids inside the vocabulary, 1 <= n_lang <= LANG_MAX, any order
+    int n_lang, B, d;                // d a multiple of 4, <= LANG_D_MAX
+    int* lang_tok;                   // [B] in: >= 0 keeps the caller's choice; out: the winning id where it was negative
+    float* lang_prob;                // [B][n_lang]
+};
+constexpr int LANG_D_MAX = 1280;
+hipError_t launch_lang_select(const LangSelectParams& p, hipStream_t s);
 // ---- temperature sampling: Gumbel-max over a counter-based generator (DESIGN.md "Temperature sampling").  Philox-4x32-10 (Salmon et al.,
 // SC'11): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped by the Weyl constants between rounds.
 __host__ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
@@ -530,6 +548,15 @@ inline int vocab_skinny_fuse_argmax(SkinnyParams& k, const SelectParams& sp) {
     k.am_ld = grid;
     return grid;
 }
+// the first step's language detection on the final hidden state `h` (the residual stream the vocabulary stage normalises too)
+inline LangSelectParams lang_select_params(const float* h, const float* ln_w, const float* ln_b, const void* emb, int emb_half, const int* lang_ids,
+                                           int n_lang, int B, int d, int* lang_tok, float* lang_prob) {
+    LangSelectParams p;
+    memset(&p, 0, sizeof p);
+    p.x = h; p.ln_w = ln_w; p.ln_b = ln_b; p.emb = (const float*)emb; p.emb_half = emb_half ? 1 : 0; p.lang_ids = lang_ids; p.n_lang = n_lang;
+    p.B = B; p.d = d; p.lang_tok = lang_tok; p.lang_prob = lang_prob;
+    return p;
+}
 inline void greedy_select_fused(SelectParams& sp, int parts) { sp.fused = 1; sp.n_parts = parts; }
 // the plain greedy tail (greedy_select_kernel's SELECT_CHUNKS partials unless greedy_select_fused follows, then greedy_finish_kernel)
 inline void greedy_select_params(SelectParams& sp, const float* logits, const uint8_t* mask, const int* forced, int* ids, int* unfinished,
@@ -544,6 +571,7 @@ inline void greedy_select_params(SelectParams& sp, const float* logits, const ui
     sp.d_model = d; sp.n_parts = SELECT_CHUNKS; sp.fused = 0; sp.emb_half = emb_half;
     sp.force_eos_rows = force_eos_rows; sp.mailbox = mailbox;
     sp.start_token = start_token;
+    sp.lang_pos = -1;
 }
 
 // ---- GemmParams of the encoder's two convolutions and of the cross-K/V projection.  engine.hip and the debug hooks (debug_api.hip) both

@@ -282,6 +282,84 @@ def _check_prompt_args(rows, vocab_size, max_length, num_beams, return_token_tim
         raise ValueError(f"a prompt of {longest} tokens, the start token and one generated token exceed max_length {max_length}")
 
 
+def language_ids_of(config: dict):
+    """The language token ids of a config: `language_ids` (synthetic models), else the values of `lang_to_id` (generation_config.json, which
+    examples/whisper/_common.py copies into the config), in ascending order.  [] when the config names none."""
+    ids = config.get("language_ids")
+    if ids is None and isinstance(config.get("lang_to_id"), dict):
+        ids = sorted(config["lang_to_id"].values())
+    return [int(t) for t in (ids or [])]
+
+
+def resolve_languages(config: dict, language, batch: int):
+    """`language=` of generate / begin as the engine takes it (wt_decoder_set_languages): returns (language_ids, rows) with rows[b] the
+    language token id of utterance b, or -1 where it is to be detected.  `language`: "auto", an id, a code ("en") or token ("<|en|>")
+    looked up in the config's `lang_to_id`, or a list of `batch` of those.  Raises ValueError for a config without language ids or
+    without a language slot at forced position 1 (a `.en` checkpoint), for a name without a map, and for an id that is not listed."""
+    ids = language_ids_of(config)
+    if not ids:
+        raise ValueError("language= needs the config's language ids (`language_ids`, or generation_config.json's `lang_to_id`)")
+    if len(ids) > 128 or len(set(ids)) != len(ids):
+        raise ValueError(f"language ids must be at most 128 distinct ids, got {len(ids)}")
+    forced = config.get("forced_decoder_ids") or []
+    if not forced or forced[0][0] != 1 or forced[0][1] not in ids:
+        raise ValueError("language= needs a forced_decoder_ids list whose position 1 is a language token (a multilingual checkpoint)")
+    entries = list(language) if isinstance(language, (list, tuple)) else [language] * batch
+    if len(entries) != batch:
+        raise ValueError(f"language has {len(entries)} entries for a batch of {batch} (one for all, or one per utterance)")
+    rows = []
+    for entry in entries:
+        if hasattr(entry, "item"):
+            entry = entry.item()
+        if entry is None or entry == "auto":
+            rows.append(-1)
+            continue
+        if isinstance(entry, str):
+            names = config.get("lang_to_id")
+            if not isinstance(names, dict):
+                raise ValueError(f"language {entry!r}: the config has no `lang_to_id` map (pass a token id)")
+            key = entry if entry.startswith("<|") else f"<|{entry}|>"
+            if key not in names:
+                raise ValueError(f"language {entry!r} is not in the config's `lang_to_id`")
+            entry = names[key]
+        if isinstance(entry, bool) or not isinstance(entry, int) or entry not in ids:
+            raise ValueError(f"language token {entry!r} is not one of the config's language ids")
+        rows.append(int(entry))
+    return ids, rows
+
+
+def resolve_task(config: dict, task):
+    """`task=` as a token id: "transcribe" / "translate" through the config's `task_to_id`, or an id (synthetic models)."""
+    if isinstance(task, str):
+        names = config.get("task_to_id")
+        if not isinstance(names, dict):
+            raise ValueError(f"task {task!r}: the config has no `task_to_id` map (pass a token id)")
+        if task not in names:
+            raise ValueError(f"task {task!r} is not in the config's `task_to_id` ({sorted(names)})")
+        task = names[task]
+    if isinstance(task, bool) or not isinstance(task, int) or not 0 <= task < config["vocab_size"]:
+        raise ValueError(f"task must be a name of `task_to_id` or a token id, got {task!r}")
+    if not any(pos == 2 for pos, _tok in (config.get("forced_decoder_ids") or [])):
+        raise ValueError("task= needs a forced_decoder_ids list with a task token at position 2 (a multilingual checkpoint)")
+    return int(task)
+
+
+class DecodeLanguages:
+    """The languages of a decode (generate(..., language=...)): `ids` int32 [B] on the GPU, every row's language token (the caller's, or
+    the detected one); `probs` float32 [B, n_lang]: softmax of the first step's logits over `language_ids`, in their order (all 0 when
+    no row was left to detect); `language_ids`: the config's list."""
+
+    def __init__(self, ids, probs, language_ids):
+        self.ids, self.probs, self.language_ids = ids, probs, list(language_ids)
+
+    def prob_of_ids(self):
+        """float32 [B]: the probability of every row's own language."""
+        import torch
+        table = torch.as_tensor(self.language_ids, device=self.ids.device)
+        col = (self.ids.long()[:, None] == table[None, :]).int().argmax(1)
+        return self.probs.gather(1, col[:, None])[:, 0]
+
+
 class DecodeScores:
     """Confidence signals of a greedy decode (generate(..., return_logprobs=True)), openai-whisper's definitions:
     `token_logprobs` float32 [B, len]: log-probability of every emitted token under the step's processed scores (0 at position 0, at
@@ -299,6 +377,18 @@ class DecodeScores:
         width = torch.full((body.shape[0],), body.shape[1], dtype=torch.int64, device=body.device)
         self.n_scored = torch.where(is_eos.any(1), is_eos.int().argmax(1) + 1, width)
         self.avg_logprob = sum_logprob / self.n_scored.clamp(min=1).to(sum_logprob.dtype)
+
+
+def _check_language_args(config, language, batch, num_beams, return_token_timestamps):
+    """What the engine refuses of `language=` (wt_decoder_begin: WT_E_INVALID, WT_E_UNSUPPORTED), refused before anything is enqueued.
+    Returns (language_ids, rows) as `resolve_languages`, or (None, None) when the mode is off."""
+    if language is None:
+        return None, None
+    if num_beams > 1:
+        raise ValueError("language= and beam search cannot be combined")
+    if return_token_timestamps:
+        raise ValueError("language= and return_token_timestamps cannot be combined")
+    return resolve_languages(config, language, batch)
 
 
 def _check_logprob_args(return_logprobs, no_speech_token_id, num_beams, vocab_size):
@@ -389,9 +479,10 @@ class WhisperDecoderEngine:
         """Another engine on the same device weights (own resident KV caches, step graphs, mailbox): for a second host thread / stream."""
         return WhisperDecoderEngine(None, self.config, _session=self.session.clone())
 
-    def _params(self, max_length, force_eos_step, logits_trace, force_eos_steps=None, return_timestamps=False, prompt_len=0):
+    def _params(self, max_length, force_eos_step, logits_trace, force_eos_steps=None, return_timestamps=False, prompt_len=0, task_id=None):
         """`prompt_len`: tokens of a decoder prompt in front of the start token -- every position of the rules is an absolute sequence
-        position, so begin_index and the forced pairs move behind the prompt (generation/utils.py:943 counts the prompt the same way)."""
+        position, so begin_index and the forced pairs move behind the prompt (generation/utils.py:943 counts the prompt the same way).
+        `task_id`: replaces the token at forced position 2 (`task=`)."""
         cfg = self.config
         begin_index = 1 if cfg.get("forced_bos_token_id") is None else 2          # run.py:155-156 with a 1-token prompt
         forced = cfg.get("forced_decoder_ids") or []
@@ -400,7 +491,7 @@ class WhisperDecoderEngine:
         if forced:
             begin_index += forced[-1][0]                                           # run.py:157
         begin_index += prompt_len
-        forced = [[pos + prompt_len, tok] for pos, tok in forced]
+        forced = [[pos + prompt_len, task_id if pos == 2 and task_id is not None else tok] for pos, tok in forced]
         p = _lib.GreedyParams()
         p.decoder_start_token_id = cfg["decoder_start_token_id"]
         p.eos_token_id, p.pad_token_id = cfg["eos_token_id"], cfg["pad_token_id"]
@@ -475,6 +566,40 @@ class WhisperDecoderEngine:
         _lib.check(self.session._lib.wt_decoder_set_prompt(self.session.handle, ctypes.byref(t) if t is not None else None), "wt_decoder_set_prompt")
         self._prompt_len = len(rows[0]) if rows else 0
 
+    def _set_languages(self, language_ids=None, rows=None):
+        """`rows`: per utterance a listed id or -1 = detect (wt_decoder_set_languages); no ids: off."""
+        if language_ids:
+            ids, n = _i32_array(language_ids)
+            tok, m = _i32_array(rows)
+            self._lang_keep = (ids, tok)
+            _lib.check(self.session._lib.wt_decoder_set_languages(self.session.handle, ctypes.cast(ids, ctypes.POINTER(ctypes.c_int32)), n,
+                                                                   ctypes.cast(tok, ctypes.POINTER(ctypes.c_int32)), m), "wt_decoder_set_languages")
+        else:
+            _lib.check(self.session._lib.wt_decoder_set_languages(self.session.handle, None, 0, None, 0), "wt_decoder_set_languages")
+        self._lang_ids = list(language_ids) if language_ids else []
+
+    def read_languages(self):
+        """DecodeLanguages of the decode in flight (wt_decoder_read_languages, stream-ordered; behind its first step)."""
+        import torch
+        dev = self._enc.device
+        tok = torch.empty(self._B, dtype=torch.int32, device=dev)
+        prob = torch.empty(self._B, len(self._lang_ids), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(self.session._lib.wt_decoder_read_languages(self.session.handle, tok.data_ptr(), prob.data_ptr(), ctypes.c_void_p(stream)),
+                   "wt_decoder_read_languages")
+        return DecodeLanguages(tok, prob, self._lang_ids)
+
+    def detect_language(self, encoder_hidden):
+        """openai-whisper's detect_language for a batch: (ids int32 [B], probs float32 [B, n_lang] over the config's language ids) on the
+        GPU -- `begin(language="auto")`, the first step, `read_languages`."""
+        import torch
+        parts = []
+        for i in range(0, encoder_hidden.shape[0], self.max_batch):
+            self.begin(encoder_hidden[i:i + self.max_batch], language="auto")
+            self.steps(1)
+            parts.append(self.read_languages())
+        return torch.cat([p.ids for p in parts]), torch.cat([p.probs for p in parts])
+
     def self_kv_head(self, layer: int, head: int, which: int = 0):
         """Debug read-back: the resident self-K (which 0) or self-V (1) rows of (layer, head), numpy float32 [B, max_target_positions, 64]."""
         import numpy as np
@@ -547,8 +672,8 @@ class WhisperDecoderEngine:
               return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0, early_stopping=False,
               return_token_timestamps: bool = False, alignment_heads=None, median_filter_width: int = 7,
               return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0, seed: int = 0, seeds=None, prompt_ids=None,
-              prompts=None):
-        """Start a decode (wt_decoder_begin).  `prompt_ids` / `prompts`: a decoder prompt in front of the start token, shared or of one length / per utterance (see `generate`).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
+              prompts=None, language=None, task=None):
+        """Start a decode (wt_decoder_begin).  `language` / `task`: per-utterance language tokens or detection, and the task token (see `generate`; read the languages with `read_languages`).  `prompt_ids` / `prompts`: a decoder prompt in front of the start token, shared or of one length / per utterance (see `generate`).  `temperature` > 0: temperature sampling on the device (wt_decoder_set_sampling), row b drawing
         with `seeds[b]`, or `seed + b` without a list; not with beams.  `return_logprobs` / `no_speech_token_id`: see `generate` (read with `read_logprobs`).  `return_timestamps`: Whisper's timestamp mode (wt_decoder_set_timestamp_rules) --
         the prompt loses <|notimestamps|> and the ids carry <|t|> tokens (ids >= timestamp_begin, t x 0.02 s).
         `num_beams` > 1: beam search on the device (wt_decoder_set_beam_search) with transformers' `length_penalty` / `early_stopping`
@@ -583,10 +708,13 @@ class WhisperDecoderEngine:
             _check_prompt_args(prompt, i.vocab_size, self.config["max_length"] if max_length is None else max_length, num_beams,
                                return_token_timestamps, i.precision != 0)
         plen = max(len(r) for r in prompt) if prompt else 0
-        self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, plen)
+        lang_ids, lang_rows = _check_language_args(self.config, language, self._B, num_beams, return_token_timestamps)
+        self._p = self._params(max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, plen,
+                               None if task is None else resolve_task(self.config, task))
         self._trace = logits_trace
         self._set_timestamp_rules(return_timestamps, plen)
         self._set_prompt(prompt, ragged=prompts is not None)
+        self._set_languages(lang_ids, lang_rows)
         self._set_beam_search(num_beams, length_penalty, early_stopping)
         self._set_token_timestamps(tt_heads, median_filter_width)
         self._set_logprobs(return_logprobs, no_speech_token_id)
@@ -656,8 +784,15 @@ class WhisperDecoderEngine:
                  lookahead: int = 0, return_timestamps: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, return_scores: bool = False, return_token_timestamps: bool = False, alignment_heads=None,
                  median_filter_width: int = 7, return_logprobs: bool = False, no_speech_token_id=None, temperature: float = 0.0,
-                 seed: int = 0, seeds=None, prompt_ids=None, prompts=None):
+                 seed: int = 0, seeds=None, prompt_ids=None, prompts=None, language=None, task=None):
         """== greedy_search(...) of run.py:171-227 for a batch; returns int32 ids [B, len] on the GPU.
+        `language`: per-utterance language tokens (include/whisper_trtllm_amd.h (9i)) for a multilingual config, whose forced list holds a
+        language token at position 1: "auto" detects every row's language in the first step of the decode (openai-whisper's
+        detect_language, without a decoder pass of its own); an id of the config's `language_ids`, a code ("en") or a token ("<|en|>") of
+        its `lang_to_id` sets it; a list gives one of those per utterance.  The result then carries a DecodeLanguages as its LAST element
+        (ids, languages) / (ids, DecodeScores, languages).  At most 16 utterances per call; not with num_beams > 1 or
+        return_token_timestamps.  `task`: "transcribe" / "translate" (the config's `task_to_id`) or a token id: replaces the token at
+        forced position 2.
         `prompts`: per-utterance decoder prompts of unequal lengths (several recordings under condition_on_previous_text): one sequence per
         utterance, each empty or starting with <|startofprev|>, cut like `prompt_ids`; not together with it.  With Lmax the longest, the
         returned rows are left-padded with pad_token_id to Lmax in front of the start token (`strip_prompts` removes pad and prompt),
@@ -687,6 +822,15 @@ class WhisperDecoderEngine:
             raise ValueError("return_scores needs num_beams > 1 (greedy decoding keeps no sequence score)")
         row_seeds = _check_sampling_args(temperature, seed, seeds, encoder_hidden, num_beams)
         samp = lambda i, j: {"temperature": temperature, "seeds": row_seeds[i:j]} if row_seeds else {}
+        lk = {}
+        if language is not None:
+            _check_language_args(self.config, language, int(encoder_hidden.shape[0]), num_beams, return_token_timestamps)
+            if encoder_hidden.shape[0] > self.max_batch:
+                raise ValueError(f"language= supports at most {self.max_batch} utterances per call")
+            lk["language"] = language
+        if task is not None:
+            resolve_task(self.config, task)
+            lk["task"] = task
         prompt = None
         if prompt_ids is not None and prompts is not None:
             raise ValueError("prompt_ids and prompts cannot be combined (one shared / equal-length prompt, or one per utterance)")
@@ -699,6 +843,8 @@ class WhisperDecoderEngine:
                 ml = self.config["max_length"] if max_length is None else max_length
                 _check_prompt_args(ragged, info.vocab_size, ml, num_beams, return_token_timestamps, info.precision != 0)
                 if encoder_hidden.shape[0] > self.max_batch:
+                    if task is not None:
+                        raise ValueError(f"task= with prompts= supports at most {self.max_batch} utterances per call")
                     return self._generate_ragged_sliced(encoder_hidden, ragged, ml, force_eos_step, logits_trace, chunk, force_eos_steps, lookahead,
                                                         return_timestamps, return_logprobs, no_speech_token_id, temperature, row_seeds)
         if prompt_ids is not None:   # (begin() checks again on the single-batch path; here the rows are also needed to slice a >16-row batch)
@@ -716,12 +862,12 @@ class WhisperDecoderEngine:
         if num_beams > 1 and encoder_hidden.shape[0] > group:   # utterances x beams <= 16 rows per engine call
             import torch
             parts = [self.generate(encoder_hidden[i:i + group], max_length, None, None, chunk, None, lookahead, False, num_beams,
-                                   length_penalty, early_stopping, True) for i in range(0, encoder_hidden.shape[0], group)]
+                                   length_penalty, early_stopping, True, **lk) for i in range(0, encoder_hidden.shape[0], group)]
             width = max(p[0].shape[1] for p in parts)
             ids = torch.cat([torch.nn.functional.pad(p[0], (0, width - p[0].shape[1]), value=self.config["pad_token_id"]) for p in parts], dim=0)
             return (ids, torch.cat([p[1] for p in parts])) if return_scores else ids
         if num_beams > 1:
-            self.begin(encoder_hidden, max_length, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping)
+            self.begin(encoder_hidden, max_length, num_beams=num_beams, length_penalty=length_penalty, early_stopping=early_stopping, **lk)
             if chunk <= 0:
                 cur, _nu = self.run(lookahead)
             else:
@@ -740,7 +886,7 @@ class WhisperDecoderEngine:
             lp = {"return_logprobs": True, "no_speech_token_id": no_speech_token_id} if return_logprobs else {}
             parts = [self.generate(encoder_hidden[i:i + self.max_batch], max_length, force_eos_step, None, chunk,
                                    None if force_eos_steps is None else force_eos_steps[i:i + self.max_batch], lookahead,
-                                   return_timestamps, **(tt or {}), **lp, **samp(i, i + self.max_batch), **pk(i, i + self.max_batch))
+                                   return_timestamps, **(tt or {}), **lp, **samp(i, i + self.max_batch), **pk(i, i + self.max_batch), **lk)
                      for i in range(0, encoder_hidden.shape[0], self.max_batch)]
             pad = self.config["pad_token_id"]
             cat = lambda ps, value: torch.cat([torch.nn.functional.pad(p, (0, max(q.shape[1] for q in ps) - p.shape[1]), value=value) for p in ps], dim=0)
@@ -755,7 +901,7 @@ class WhisperDecoderEngine:
                 return cat([p[0] for p in parts], pad), cat([p[1] for p in parts], 0.0)
             return cat(parts, pad)
         self.begin(encoder_hidden, max_length, force_eos_step, logits_trace, force_eos_steps, return_timestamps, **(tt or {}),
-                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id, **samp(0, None), **pk(0, None))
+                   return_logprobs=return_logprobs, no_speech_token_id=no_speech_token_id, **samp(0, None), **pk(0, None), **lk)
         if chunk <= 0:
             cur, _nu = self.run(lookahead)
         else:
@@ -764,11 +910,14 @@ class WhisperDecoderEngine:
             while not done and cur < ml:
                 self.steps(min(chunk, ml - cur))
                 cur, _nu, done = self.poll()
+        langs = (self.read_languages(),) if language is not None else ()
         if return_logprobs:
             ids = self.read_ids(cur)
             scores = self.read_logprobs(ids)
-            return (ids, self.read_token_timestamps(cur), scores) if tt else (ids, scores)
-        return (self.read_ids(cur), self.read_token_timestamps(cur)) if tt else self.read_ids(cur)
+            return (ids, self.read_token_timestamps(cur), scores) + langs if tt else (ids, scores) + langs
+        if tt:
+            return (self.read_ids(cur), self.read_token_timestamps(cur)) + langs
+        return (self.read_ids(cur),) + langs if langs else self.read_ids(cur)
 
     def _generate_ragged_sliced(self, encoder_hidden, rows, max_length, force_eos_step, logits_trace, chunk, force_eos_steps, lookahead,
                                 return_timestamps, return_logprobs, no_speech_token_id, temperature, row_seeds):
@@ -809,7 +958,9 @@ class WhisperDecoderEngine:
         temperature (or with `seeds[i]`, for a caller whose rows are not consecutive utterances), whichever other rows are decoded beside
         it.  `text_of(ids) -> str` gives the text whose compression ratio is taken
         (default: the config's token decoder, or the ids in decimal).  `prompt_ids` (see `generate`) goes to every try; the EOS is searched
-        behind the prompt and the compression ratio is taken of the text without it.  `prompts` (per-utterance, see `generate`): a try
+        behind the prompt and the compression ratio is taken of the text without it.  `language` / `task` (see `generate`): the first try
+        detects or sets the rows' languages, every later try decodes its rows with the languages of the first; the result then ends with
+        the DecodeLanguages of the first try.  `prompts` (per-utterance, see `generate`): a try
         decodes its rows left-padded to ITS longest prompt, with max_length lowered by what that is shorter than the whole batch's -- every
         row keeps its budget of generated tokens and, drawing at its own positions, its result whichever rows are tried beside it; the
         returned rows are all left-padded to the whole batch's longest.  Returns (ids int32 [B, len] padded with pad_token_id, DecodeScores,
@@ -828,6 +979,13 @@ class WhisperDecoderEngine:
         row_seed = [int(seed) + i for i in range(B)] if seeds is None else [int(x) for x in seeds]
         if len(row_seed) < B:
             raise ValueError(f"seeds needs one entry per utterance ({B}), got {len(row_seed)}")
+        language = generate_kwargs.pop("language", None)
+        langs = None
+        if language is not None:
+            if B > self.max_batch:
+                raise ValueError(f"language= supports at most {self.max_batch} utterances per call")
+            resolve_languages(self.config, language, B)
+        lang_of = lambda rows: {} if language is None else {"language": language if langs is None else [int(found[i]) for i in rows]}
         prompt = generate_kwargs.pop("prompt_ids", None)
         ragged = generate_kwargs.pop("prompts", None)
         if prompt is not None and ragged is not None:
@@ -851,15 +1009,20 @@ class WhisperDecoderEngine:
             if ragged:   # this try's rows at their own longest prompt, then shifted to the whole batch's
                 sub = [ragged[i] for i in todo]
                 shift = plen - max(len(r) for r in sub)
-                ids, sc = self.generate(hidden, max_length=ml - shift, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
-                                        seeds=[row_seed[i] for i in todo], **generate_kwargs, prompts=sub)
+                out = self.generate(hidden, max_length=ml - shift, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
+                                    seeds=[row_seed[i] for i in todo], **generate_kwargs, prompts=sub, **lang_of(todo))
+                ids, sc = out[0], out[1]
                 if shift:
                     ids = torch.nn.functional.pad(ids, (shift, 0), value=pad)
                     sc.token_logprobs = torch.nn.functional.pad(sc.token_logprobs, (shift, 0), value=0.0)
             else:
-                ids, sc = self.generate(hidden, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
-                                        seeds=[row_seed[i] for i in todo], **generate_kwargs,
-                                        **({"prompt_ids": prompt if len(prompt) == 1 else [prompt[i] for i in todo]} if prompt else {}))
+                out = self.generate(hidden, return_logprobs=True, no_speech_token_id=no_speech_token_id, temperature=t,
+                                    seeds=[row_seed[i] for i in todo], **generate_kwargs, **lang_of(todo),
+                                    **({"prompt_ids": prompt if len(prompt) == 1 else [prompt[i] for i in todo]} if prompt else {}))
+                ids, sc = out[0], out[1]
+            if language is not None and langs is None:   # the first try covers every row: its languages are the decode's
+                langs = out[2]
+                found = langs.ids.cpu().tolist()
             avg = sc.avg_logprob.cpu().tolist()
             nsp = sc.no_speech_prob.cpu().tolist() if sc.no_speech_prob is not None else [None] * len(todo)
             host_ids = ids.cpu().tolist()
@@ -887,7 +1050,8 @@ class WhisperDecoderEngine:
         ids = torch.stack([padded(r[0], pad) for r in rows])
         scores = DecodeScores(ids, torch.stack([padded(r[1], 0.0) for r in rows]), torch.stack([r[2] for r in rows]),
                               torch.stack([r[3] for r in rows]) if rows[0][3] is not None else None, eos, plen)
-        return ids, scores, torch.tensor([r[4] for r in rows], dtype=torch.float32, device=ids.device)
+        temps = torch.tensor([r[4] for r in rows], dtype=torch.float32, device=ids.device)
+        return (ids, scores, temps, langs) if language is not None else (ids, scores, temps)
 
     def stream(self, slots: int = 8, pool_rows: int = 0, max_length=None, return_timestamps: bool = False, num_beams: int = 1,
                return_token_timestamps: bool = False) -> "DecodeStream":
@@ -952,6 +1116,7 @@ class DecodeStream:
         dec._set_token_timestamps(())       # ... and a decode with token-level timestamps
         dec._set_sampling(0.0)              # ... and a sampled decode
         dec._set_prompt(None)               # ... and a decode behind a prompt
+        dec._set_languages(None)            # ... and a decode with per-row languages
         self.pool_rows = int(pool_rows) if pool_rows else 4 * self.slots
         stream = torch.cuda.current_stream().cuda_stream
         _lib.check(self._lib.wt_decoder_stream_begin(self._h, self.slots, self.pool_rows, ctypes.byref(self._p), ctypes.c_void_p(stream)),
